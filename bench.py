@@ -2,8 +2,10 @@
 on synthetic 10 000-point clouds (BASELINE.json).  One process per GPU; for N > 1 launch with
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line.  See DESIGN.md (Measurement) for the definitions of ``roofline``
-and ``cpu_baseline``.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line;
+``--full`` adds the dense mean-shift re-run (``value_dense``), the profiled steps (``kernels``,
+``roofline``) and ``cpu_baseline`` — see DESIGN.md (Measurement) for their definitions.
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -440,6 +442,37 @@ def launch_ranks(gpus):
     return rc
 
 
+DUMP_MAX_ELEMENTS = 4_000_000     # per array: 16 MB of float32; larger arrays are written as a fixed, seeded sample
+
+
+def dump_outputs(step, loss, out_dir):
+    """``--dump-outputs DIR``: what the last timed step computed, as DIR/<name>.npy (float32 / float64) — the
+    loss the step returned, the flat gradient it reduced, the parameters after its optimizer step and the
+    per-term losses the workload keeps (cfg5: the fitting residual; cfg2 / cfg3: Chamfer, regression, Laplacian).
+    The inputs are fixed by the arguments, so two builds can be compared output for output.  An array with more
+    than DUMP_MAX_ELEMENTS entries is replaced by the same seeded sample of its entries in every run."""
+    import numpy as np
+    arrays = {"loss": loss}
+    bucket = getattr(step, "bucket", None)
+    if bucket is not None:
+        arrays["grad"] = bucket.flat
+    arrays["params"] = torch.cat([p.detach().reshape(-1) for p in step.model.parameters()])
+    if torch.is_tensor(getattr(step, "last_res", None)):
+        arrays["residual"] = step.last_res
+    for name, t in zip(("chamfer", "regression", "laplacian"), getattr(step, "last", None) or ()):
+        if torch.is_tensor(t):
+            arrays[name] = t
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        a = a.reshape(-1) if a.ndim else a.reshape(1)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_selftest():
     """--selftest-launch: every rank joins the process group (gloo when no GPU is visible), the
     ranks count themselves with one all-reduce, rank 0 prints the JSON line.  Lets the CPU test
@@ -476,8 +509,15 @@ def main():
     ap.add_argument("--host-threads", type=int, default=int(os.environ.get("PARSENET_HOST_THREADS", "1")),
                     help="torch intra-op CPU threads while the GPU legs run (default 1, see dp.limit_host_threads; 0: "
                          "torch's default of one per visible core); the CPU baseline gets the usable CPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cfg5's second timed run with dense mean-shift "
+                         "launches (value_dense), the profiled steps (kernels, kernel_ms_per_step, roofline) and the "
+                         "CPU baseline.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    full = args.full or args.profile_only      # --profile-only IS the profiled pass
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))     # before anything touches the GPU
@@ -523,6 +563,7 @@ def main():
             step.cursor = snap["cursor"]
 
     per_rank = {}
+    last_loss = []            # what the last timed step returned (--dump-outputs)
 
     def timed_run(tag="default"):
         """W untimed + K timed steps, barrier + synchronize on both sides, MAX over ranks.  Every rank also
@@ -534,8 +575,9 @@ def main():
             step.step()
         barrier()
         t0 = time.perf_counter()
+        loss = None
         for _ in range(args.steps):
-            step.step()
+            loss = step.step()
         sync()
         own = time.perf_counter() - t0
         barrier()
@@ -553,6 +595,7 @@ def main():
             own_lo = own_hi = own
         per_rank[tag] = {"min": round(1e3 * own_lo / max(args.steps, 1), 3),
                          "max": round(1e3 * own_hi / max(args.steps, 1), 3)}
+        last_loss[:] = [loss]
         return el
 
     # every run (default launches, dense launches, profiled steps) starts from the pre-trained state.
@@ -580,8 +623,10 @@ def main():
         sync()
         restore(start)
     elapsed = None if args.profile_only else timed_run()
+    if args.dump_outputs and rank == 0 and last_loss and last_loss[0] is not None:
+        dump_outputs(step, last_loss[0], args.dump_outputs)
 
-    # cfg5: the same steps once more with every mean-shift launch dense (PARSENET_MS_SPARSE=0 at run
+    # --full, cfg5: the same steps once more with every mean-shift launch dense (PARSENET_MS_SPARSE=0 at run
     # time): the block-sparse plans are data dependent, the dense value is their floor
     elapsed_dense = None
     ms_mode = None
@@ -593,7 +638,7 @@ def main():
             calls_timed = dict(_ms.CALLS)
             if args.profile_only:          # no timed steps to take the kind from: the environment decides
                 calls_timed = {"planned": 0 if ms_mode is False else 1, "dense": 1 if ms_mode is False else 0}
-    if ((ms_mode not in (None, False) and not args.no_dense) or stub) and not args.profile_only:
+    if ((ms_mode not in (None, False) and not args.no_dense) or stub) and args.full and not args.profile_only:
         restore(start)
         if ms_mode is not None:
             _ms.SPARSE = False
@@ -607,56 +652,58 @@ def main():
     # (only rank 0 keeps the per-kernel table), otherwise rank 0 would pair its all-reduce with
     # the other ranks' barrier.  Default: one pass over the timed pool.  Their mean-shift launches
     # are of ONE kind — the kind most timed steps used — so that a kernel family's average launch
-    # duration and its executed work belong together.
-    restore(start)
-    nprof = args.profile_steps
-    if nprof < 0:
-        nprof = max(1, getattr(step, "pool", step.batch) // step.batch)
-    census = None
-    if ms_mode is not None:
-        tally = torch.tensor([calls_timed["planned"], calls_timed["dense"]], dtype=torch.float64, device=device)
-        if multi:     # ONE decision for all ranks: the steps below contain collectives
-            dist.all_reduce(tally)
-        mostly_planned = bool(tally[0] > tally[1])
-        _ms.SPARSE = mostly_planned
-    try:
-        roof, table = (None, {}) if stub else kernel_roofline(step, nprof)
-        if ms_mode is not None and not mostly_planned and not args.profile_only:
-            # the plans of the timed pool all the same (one planned pass, not timed, not profiled):
-            # how much of the dense work a planned launch WOULD execute on this embedding
-            restore(start)
-            _ms.SPARSE = True
-            os.environ["PARSENET_MS_STATS"] = "1"
-            fr = []
-            for _ in range(max(1, step.pool // step.batch)):
-                _ms.LAST_PLAN_STATS = None
-                step.step()
-                if _ms.LAST_PLAN_STATS:
-                    fr.append(sum(t[0] for t in _ms.LAST_PLAN_STATS) / len(_ms.LAST_PLAN_STATS))
-            os.environ.pop("PARSENET_MS_STATS", None)
-            torch.cuda.synchronize()
-            if fr:
-                census = {"tile_pairs_a_plan_would_keep": {"min": min(fr), "mean": sum(fr) / len(fr), "max": max(fr)},
-                          "steps_sampled": len(fr)}
-    finally:
+    # duration and its executed work belong together.  Only with --full (--profile-only is this pass alone).
+    roof, table, census, nprof = None, {}, None, 0
+    if full:
+        restore(start)
+        nprof = args.profile_steps
+        if nprof < 0:
+            nprof = max(1, getattr(step, "pool", step.batch) // step.batch)
         if ms_mode is not None:
-            _ms.SPARSE = ms_mode
-    if ms_mode is not None and roof is not None:
-        roof["meanshift_launches"] = {
-            "mode": {True: "planned (PARSENET_MS_SPARSE=1)", False: "dense (PARSENET_MS_SPARSE=0)"}.get(
-                ms_mode, "auto: plan %d calls, go dense for %d calls when their plans keep more than %.2f of the "
-                         "tile pairs on average" % (_ms.AUTO_SAMPLES, _ms.AUTO_DENSE_STEPS, _ms.AUTO_DENSE_ABOVE)),
-            "timed_and_warmup_calls": calls_timed, "profiled_as": "planned" if mostly_planned else "dense"}
-        if census:
-            roof["meanshift_launches"].update(census)
-    if stub:
-        for _ in range(nprof):
-            step.step()
-    # The CPU baseline: rank 0, outside every timed region (with several ranks the others wait at the barrier
+            tally = torch.tensor([calls_timed["planned"], calls_timed["dense"]], dtype=torch.float64, device=device)
+            if multi:     # ONE decision for all ranks: the steps below contain collectives
+                dist.all_reduce(tally)
+            mostly_planned = bool(tally[0] > tally[1])
+            _ms.SPARSE = mostly_planned
+        try:
+            roof, table = (None, {}) if stub else kernel_roofline(step, nprof)
+            if ms_mode is not None and not mostly_planned and not args.profile_only:
+                # the plans of the timed pool all the same (one planned pass, not timed, not profiled):
+                # how much of the dense work a planned launch WOULD execute on this embedding
+                restore(start)
+                _ms.SPARSE = True
+                os.environ["PARSENET_MS_STATS"] = "1"
+                fr = []
+                for _ in range(max(1, step.pool // step.batch)):
+                    _ms.LAST_PLAN_STATS = None
+                    step.step()
+                    if _ms.LAST_PLAN_STATS:
+                        fr.append(sum(t[0] for t in _ms.LAST_PLAN_STATS) / len(_ms.LAST_PLAN_STATS))
+                os.environ.pop("PARSENET_MS_STATS", None)
+                torch.cuda.synchronize()
+                if fr:
+                    census = {"tile_pairs_a_plan_would_keep": {"min": min(fr), "mean": sum(fr) / len(fr),
+                                                               "max": max(fr)},
+                              "steps_sampled": len(fr)}
+        finally:
+            if ms_mode is not None:
+                _ms.SPARSE = ms_mode
+        if ms_mode is not None and roof is not None:
+            roof["meanshift_launches"] = {
+                "mode": {True: "planned (PARSENET_MS_SPARSE=1)", False: "dense (PARSENET_MS_SPARSE=0)"}.get(
+                    ms_mode, "auto: plan %d calls, go dense for %d calls when their plans keep more than %.2f of the "
+                             "tile pairs on average" % (_ms.AUTO_SAMPLES, _ms.AUTO_DENSE_STEPS, _ms.AUTO_DENSE_ABOVE)),
+                "timed_and_warmup_calls": calls_timed, "profiled_as": "planned" if mostly_planned else "dense"}
+            if census:
+                roof["meanshift_launches"].update(census)
+        if stub:
+            for _ in range(nprof):
+                step.step()
+    # --full: the CPU baseline, rank 0, outside every timed region (with several ranks the others wait at the barrier
     # below: a bounded sample, <= 45 s).  The stub workload reports a token entry so that the multi-rank control
     # flow of this leg is covered on gloo ranks too.
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and not args.profile_only:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not args.profile_only:
         if stub:
             cpu = {"value": None, "unit": "shapes/s", "cores": 1, "kind": "port", "sample": "stub workload: none"}
         else:
@@ -697,10 +744,10 @@ def main():
                            **({"meanshift_products": _ms_arith()} if args.workload == "cfg5" else {})),
             "roofline": roof,
             "cpu_baseline": cpu,
-            "kernels": {k: round(v["avg_ms"], 4) for k, v in sorted(table.items())},
+            "kernels": {k: round(v["avg_ms"], 4) for k, v in sorted(table.items())} if full else None,
             # the same families as GPU milliseconds per step (avg launch x launches per step; launches in brackets)
             "kernel_ms_per_step": {k: [round(v["ms_total"] / max(nprof, 1), 3), round(v["calls"] / max(nprof, 1), 1)]
-                                   for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms_total"])},
+                                   for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms_total"])} if full else None,
         }
         if getattr(step, "skipped_steps", 0):
             # a rank's fitting stage raised: the step was dropped on EVERY rank (no reduction, no

@@ -188,7 +188,7 @@ def test_bench_whole_control_flow_on_two_gloo_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "stub",
-                        "--steps", "6", "--warmup", "2", "--pretrain", "5"],
+                        "--steps", "6", "--warmup", "2", "--pretrain", "5", "--full"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -198,7 +198,8 @@ def test_bench_whole_control_flow_on_two_gloo_ranks():
     assert rec["value"] > 0 and rec["value_dense"] > 0 and rec["config"]["global_batch"] == 8
     # the same on one rank (no process group at all)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stub", "--steps", "3",
-                        "--warmup", "1", "--pretrain", "2"], capture_output=True, text=True, env=env, timeout=300)
+                        "--warmup", "1", "--pretrain", "2", "--full"], capture_output=True, text=True, env=env,
+                       timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["n_gpus"] == 1
 
@@ -248,7 +249,7 @@ def test_bench_control_flow_on_four_gloo_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--workload", "stub",
-                        "--steps", "5", "--warmup", "2", "--pretrain", "3"],
+                        "--steps", "5", "--warmup", "2", "--pretrain", "3", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -258,6 +259,41 @@ def test_bench_control_flow_on_four_gloo_ranks():
     pr = rec["per_rank_ms"]
     assert 0 < pr["min"] <= pr["max"] <= rec["ms_per_step"] * 1.001
 
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run (no --full) does the timed steps and nothing else measured: no dense re-run, no profiled
+    steps, no CPU baseline.  --steps sets the number of timed steps, ms_per_step is one of them, and --dump-outputs
+    writes what the last timed step computed as float .npy files, the same in two processes with the same
+    arguments."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    recs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stub", "--steps", "4",
+                            "--warmup", "1", "--pretrain", "2", "--dump-outputs", str(tmp_path / tag)],
+                           capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec["steps"] == 4 and rec["warmup"] == 1 and rec["value"] > 0
+    elapsed_s = 4 * 4 / rec["value"]                      # 4 stub shapes per step, 4 timed steps
+    assert abs(rec["ms_per_step"] - 1e3 * elapsed_s / 4) <= 1e-6 * rec["ms_per_step"]
+    assert "value_dense" not in rec and rec["cpu_baseline"] is None and rec["roofline"] is None
+    assert rec["kernels"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"loss.npy", "grad.npy", "params.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
 
 def _status_worker(rank, w, port, out):
     import torch

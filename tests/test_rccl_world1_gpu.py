@@ -61,7 +61,7 @@ def test_bench_line_through_the_forced_collective_path(gpu):
     """`bench.py --workload cfg4 --steps 3` with WORLD_SIZE=1 and the collectives forced: barrier-bracketed timing,
     MAX over ranks with all-reduces on the device, the profiled steps with their all-reduce, process-group teardown."""
     out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg4", "--steps", "3", "--warmup", "1",
-                "--no-cpu-baseline", "--profile-steps", "1"], True)
+                "--no-cpu-baseline", "--profile-steps", "1", "--full"], True)
     assert out["n_gpus"] == 1 and out["world_size_observed"] == 1
     assert out["value"] > 0 and out["steps"] == 3
     assert out["config"].get("collective") == "forced on one rank (PARSENET_FORCE_COLLECTIVE=1)"

@@ -18,13 +18,13 @@ timeout 1800 python -m pytest tests -m gpu -q -s --durations=10 > $O/pytest.log 
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "rc $?" >> $O/smoke.log
 for W in cfg2 cfg3 cfg4; do timeout 300 python tools/determinism_probe.py --workload $W --steps 3 > $O/det_$W.txt 2>&1; done
 timeout 600 python tools/determinism_probe.py --workload cfg5 --pretrain 40 --steps 3 > $O/det_cfg5.txt 2>&1
-timeout 1200 python bench.py > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-timeout 1200 python bench.py --no-cpu-baseline > $O/bench_cfg5_b.json 2> $O/bench_cfg5_b.err
+timeout 1200 python bench.py --full > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+timeout 1200 python bench.py --full --no-cpu-baseline > $O/bench_cfg5_b.json 2> $O/bench_cfg5_b.err
 export PARSENET_PRETRAIN_CACHE=/tmp/pretrain_cache_r05.pt
-timeout 900 python bench.py --no-cpu-baseline > $O/bench_cfg5_c.json 2> $O/bench_cfg5_c.err
-timeout 600 python bench.py --workload cfg4 --steps 30 --warmup 5 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-timeout 600 python bench.py --workload cfg2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 600 python bench.py --workload cfg3 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_cfg5_c.json 2> $O/bench_cfg5_c.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --warmup 5 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout 600 python bench.py --full --workload cfg2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 600 python bench.py --full --workload cfg3 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 cd /tmp
 # (a) the default: mean-shift backward through the centre rows only — of the matrix-core mean-shift kernels only the
 #     forward pass runs; kernel statistics + SQ counters of two --profile-only processes
@@ -51,9 +51,9 @@ for C in FETCH_SIZE WRITE_SIZE; do
 PARSENET_MS_SPARSE=0 timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_${C}_dense -o p -- python3 $R/bench.py --profile-only > /dev/null 2>&1
 done
 unset PARSENET_MS_ROWS_BWD
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s4 -o b -- python3 $R/bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 > $O/prof4.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s4 -o b -- python3 $R/bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 > $O/prof4.log 2>&1
 for W in cfg2 cfg3; do
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$W -o b -- python3 $R/bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --profile-steps 0 > $O/prof_$W.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$W -o b -- python3 $R/bench.py --full --workload $W --steps 20 --warmup 5 --no-cpu-baseline --profile-steps 0 > $O/prof_$W.log 2>&1
 done
 fi
 cd $R
@@ -67,7 +67,7 @@ python tools/roofline_check.py $O/po_stats_dense.json $Kd $Cd $O/roofline_check_
 fi
 python tools/step_breakdown.py $O/s5_trace.csv > $O/breakdown_profile_only.txt 2>&1
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o b -- python3 $R/bench.py --no-cpu-baseline --no-dense --profile-steps 0 --steps 8 --warmup 3 > $O/bench_traced.json 2> $O/bench_traced.err
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o b -- python3 $R/bench.py --full --no-cpu-baseline --no-dense --profile-steps 0 --steps 8 --warmup 3 > $O/bench_traced.json 2> $O/bench_traced.err
 cd $R
 T=$(find $O/tr -name "b_kernel_trace.csv" | head -1)
 python tools/step_timeline.py $T 1 1 > $O/timeline.txt 2>&1

@@ -18,13 +18,13 @@ timeout 1800 python -m pytest tests -m gpu -q -s --durations=10 > $O/pytest.log 
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "rc $?" >> $O/smoke.log
 for W in cfg2 cfg3 cfg4; do timeout 300 python tools/determinism_probe.py --workload $W --steps 3 > $O/det_$W.txt 2>&1; done
 timeout 600 python tools/determinism_probe.py --workload cfg5 --pretrain 40 --steps 3 > $O/det_cfg5.txt 2>&1
-timeout 1200 python bench.py > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-timeout 1200 python bench.py --no-cpu-baseline > $O/bench_cfg5_b.json 2> $O/bench_cfg5_b.err
+timeout 1200 python bench.py --full > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+timeout 1200 python bench.py --full --no-cpu-baseline > $O/bench_cfg5_b.json 2> $O/bench_cfg5_b.err
 export PARSENET_PRETRAIN_CACHE=/tmp/pretrain_cache_r06.pt
-timeout 900 python bench.py --no-cpu-baseline > $O/bench_cfg5_c.json 2> $O/bench_cfg5_c.err
-timeout 600 python bench.py --workload cfg4 --steps 30 --warmup 5 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-timeout 600 python bench.py --workload cfg2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 600 python bench.py --workload cfg3 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_cfg5_c.json 2> $O/bench_cfg5_c.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --warmup 5 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout 600 python bench.py --full --workload cfg2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 600 python bench.py --full --workload cfg3 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 cd /tmp
 # (a) the default: mean-shift backward through the centre rows only — of the matrix-core mean-shift kernels only the
 #     forward pass runs; kernel statistics + SQ counters of two --profile-only processes
@@ -39,9 +39,9 @@ done
 if [ -z "$EVIDENCE_SHORT" ]; then
 # (the dense backward passes — PARSENET_MS_ROWS_BWD=0, callers with a dense gradient — are unchanged since round 5:
 #  profiles/r05_*dense* stay valid)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s4 -o b -- python3 $R/bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 > $O/prof4.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s4 -o b -- python3 $R/bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --profile-steps 0 > $O/prof4.log 2>&1
 for W in cfg2 cfg3; do
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$W -o b -- python3 $R/bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --profile-steps 0 > $O/prof_$W.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$W -o b -- python3 $R/bench.py --full --workload $W --steps 20 --warmup 5 --no-cpu-baseline --profile-steps 0 > $O/prof_$W.log 2>&1
 done
 fi
 cd $R
@@ -49,7 +49,7 @@ K=$(find $O/s5 -name "b_kernel_stats.csv" | head -1); C=$(find $O/pmc_SQ_rows -n
 python tools/roofline_check.py $O/po_stats.json $K $C $O/roofline_check.txt > /dev/null
 python tools/step_breakdown.py $O/s5_trace.csv > $O/breakdown_profile_only.txt 2>&1
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o b -- python3 $R/bench.py --no-cpu-baseline --no-dense --profile-steps 0 --steps 8 --warmup 3 > $O/bench_traced.json 2> $O/bench_traced.err
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o b -- python3 $R/bench.py --full --no-cpu-baseline --no-dense --profile-steps 0 --steps 8 --warmup 3 > $O/bench_traced.json 2> $O/bench_traced.err
 cd $R
 T=$(find $O/tr -name "b_kernel_trace.csv" | head -1)
 python tools/step_timeline.py $T 1 1 > $O/timeline.txt 2>&1
@@ -70,7 +70,7 @@ if [ -z "$EVIDENCE_SHORT" ]; then
 timeout 900 python tools/kbench.py edge chamfer smallk wgrad eval > $O/kbench.log 2>&1
 timeout 300 python tools/probes/clock_under_load.py 4 > $O/clock_sysfs.txt 2>&1
 # the data-parallel machinery forced on the one rank (RCCL process group, broadcast, all-reduce, barriers)
-PARSENET_FORCE_COLLECTIVE=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_forced_collective.json 2> $O/bench_cfg5_forced_collective.err
+PARSENET_FORCE_COLLECTIVE=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_forced_collective.json 2> $O/bench_cfg5_forced_collective.err
 timeout 600 python tools/torch_sites.py > $O/torch_sites.txt 2>&1
 timeout 600 python tools/host_cprofile.py > $O/host_cprofile.txt 2>&1
 timeout 600 python tools/probes/op_lines.py > $O/op_lines.txt 2>&1

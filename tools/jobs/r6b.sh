@@ -10,14 +10,14 @@ timeout 900 python -m pytest tests/test_gemm_gpu.py tests/test_encoder_gpu.py te
 timeout 600 python tools/kbench.py chamfer wgrad gemm > $O/kbench.log 2>&1
 export PARSENET_PRETRAIN_CACHE=/tmp/pre_x3.pt
 for rep in 1 2; do
-PARSENET_GEMM_X3=1 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_x3_$rep.json 2> $O/bench_cfg5_x3_$rep.err
-PARSENET_PRETRAIN_CACHE=/tmp/pre_fr.pt PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_frozen_$rep.json 2> $O/bench_cfg5_frozen_$rep.err
+PARSENET_GEMM_X3=1 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_x3_$rep.json 2> $O/bench_cfg5_x3_$rep.err
+PARSENET_PRETRAIN_CACHE=/tmp/pre_fr.pt PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_frozen_$rep.json 2> $O/bench_cfg5_frozen_$rep.err
 done
-PARSENET_GEMM_X3=1 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_x3.json 2> $O/bench_cfg4_x3.err
-PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_frozen.json 2> $O/bench_cfg4_frozen.err
+PARSENET_GEMM_X3=1 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_x3.json 2> $O/bench_cfg4_x3.err
+PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_frozen.json 2> $O/bench_cfg4_frozen.err
 for W in cfg2 cfg3; do
-PARSENET_GEMM_X3=1 timeout 600 python bench.py --workload $W --no-cpu-baseline > $O/bench_${W}_x3.json 2> $O/bench_${W}_x3.err
-PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 600 python bench.py --workload $W --no-cpu-baseline > $O/bench_${W}_frozen.json 2> $O/bench_${W}_frozen.err
+PARSENET_GEMM_X3=1 timeout 600 python bench.py --full --workload $W --no-cpu-baseline > $O/bench_${W}_x3.json 2> $O/bench_${W}_x3.err
+PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 timeout 600 python bench.py --full --workload $W --no-cpu-baseline > $O/bench_${W}_frozen.json 2> $O/bench_${W}_frozen.err
 done
 unset PARSENET_PRETRAIN_CACHE
 timeout 2400 python -m pytest tests/test_parity_fullsize_bwd_gpu.py tests/test_fullsize_gpu.py tests/test_e2e_gpu.py tests/test_trainer_gpu.py tests/test_determinism_gpu.py tests/test_golden_gpu.py tests/test_fitting_batch_gpu.py -m gpu -q -s > $O/pytest_whole.log 2>&1; echo "rc $?" >> $O/pytest_whole.log

@@ -9,14 +9,14 @@ timeout 900 python -m pytest tests/test_chamfer_gpu.py tests/test_gemm_gpu.py te
 timeout 600 python tools/kbench.py chamfer wgrad > $O/kbench.log 2>&1
 timeout 300 python tools/probes/clock_under_load.py 4 > $O/clock_under_load.txt 2>&1
 for rep in 1 2; do
-PARSENET_PRETRAIN_CACHE=/tmp/pre_x3.pt timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_x3_$rep.json 2> $O/bench_cfg5_x3_$rep.err
-PARSENET_PRETRAIN_CACHE=/tmp/pre_fr.pt PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 PN_CHAMFER_MFMA=0 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_r5_$rep.json 2> $O/bench_cfg5_r5_$rep.err
+PARSENET_PRETRAIN_CACHE=/tmp/pre_x3.pt timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_x3_$rep.json 2> $O/bench_cfg5_x3_$rep.err
+PARSENET_PRETRAIN_CACHE=/tmp/pre_fr.pt PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 PN_CHAMFER_MFMA=0 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_r5_$rep.json 2> $O/bench_cfg5_r5_$rep.err
 done
-timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_x3.json 2> $O/bench_cfg4_x3.err
-PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_r5.json 2> $O/bench_cfg4_r5.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_x3.json 2> $O/bench_cfg4_x3.err
+PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_r5.json 2> $O/bench_cfg4_r5.err
 for W in cfg2 cfg3; do
-timeout 600 python bench.py --workload $W --no-cpu-baseline > $O/bench_${W}_x3.json 2> $O/bench_${W}_x3.err
-PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 PN_CHAMFER_MFMA=0 timeout 600 python bench.py --workload $W --no-cpu-baseline > $O/bench_${W}_r5.json 2> $O/bench_${W}_r5.err
+timeout 600 python bench.py --full --workload $W --no-cpu-baseline > $O/bench_${W}_x3.json 2> $O/bench_${W}_x3.err
+PARSENET_GEMM_X3=frozen PARSENET_GEMM_X3_MIN_ROWS=512 PARSENET_FLAT_ADAM=0 PN_CHAMFER_MFMA=0 timeout 600 python bench.py --full --workload $W --no-cpu-baseline > $O/bench_${W}_r5.json 2> $O/bench_${W}_r5.err
 done
 # re-pin search
 for P in 600 700 800; do

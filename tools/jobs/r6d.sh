@@ -6,10 +6,10 @@ export TMPDIR=/tmp
 O=gpurun_out/r6d; mkdir -p $O
 timeout 600 python tools/kbench.py chamfer > $O/kbench.log 2>&1
 timeout 2400 python -m pytest tests -m gpu -q --durations=12 > $O/pytest.log 2>&1; echo "rc $?" >> $O/pytest.log
-timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-timeout 600 python bench.py --workload cfg2 --no-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 600 python bench.py --workload cfg3 --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout 600 python bench.py --full --workload cfg2 --no-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 600 python bench.py --full --workload cfg3 --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 cat $O/kbench.log | cut -c1-300; tail -25 $O/pytest.log
 for f in $O/bench_*.json; do echo $f; python -c "
 import json,sys

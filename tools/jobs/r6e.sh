@@ -9,14 +9,14 @@ timeout 2400 python -m pytest tests/test_knn_gpu.py tests/test_edgeconv_gpu.py t
 timeout 600 python tools/kbench.py knn chamfer > $O/kbench.log 2>&1
 export PARSENET_PRETRAIN_CACHE=/tmp/pre_e.pt
 for rep in 1 2; do
-timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_new_$rep.json 2> $O/bench_cfg5_new_$rep.err
-PN_KNN_X3_P1=6 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_p1six_$rep.json 2> $O/bench_cfg5_p1six_$rep.err
-PARSENET_CSR_PREFETCH=0 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_nocsr_$rep.json 2> $O/bench_cfg5_nocsr_$rep.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_new_$rep.json 2> $O/bench_cfg5_new_$rep.err
+PN_KNN_X3_P1=6 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_p1six_$rep.json 2> $O/bench_cfg5_p1six_$rep.err
+PARSENET_CSR_PREFETCH=0 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_nocsr_$rep.json 2> $O/bench_cfg5_nocsr_$rep.err
 done
 for rep in 1 2; do
-timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_new_$rep.json 2> $O/bench_cfg4_new_$rep.err
-PN_KNN_X3_P1=6 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p1six_$rep.json 2> $O/bench_cfg4_p1six_$rep.err
-PARSENET_CSR_PREFETCH=0 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_nocsr_$rep.json 2> $O/bench_cfg4_nocsr_$rep.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_new_$rep.json 2> $O/bench_cfg4_new_$rep.err
+PN_KNN_X3_P1=6 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p1six_$rep.json 2> $O/bench_cfg4_p1six_$rep.err
+PARSENET_CSR_PREFETCH=0 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_nocsr_$rep.json 2> $O/bench_cfg4_nocsr_$rep.err
 done
 tail -30 $O/pytest.log; cut -c1-250 $O/kbench.log
 for f in $O/bench_*.json; do echo $f; python -c "

@@ -11,13 +11,13 @@ timeout 300 python tools/kbench.py knn > $O/kbench_centre.log 2>&1
 PN_KNN_X3_CENTRE=0 timeout 300 python tools/kbench.py knn > $O/kbench_nocentre.log 2>&1
 export PARSENET_PRETRAIN_CACHE=/tmp/pre_f.pt
 for rep in 1 2; do
-timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_centre_$rep.json 2> $O/bench_cfg4_centre_$rep.err
-PN_KNN_X3_CENTRE=0 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_nocentre_$rep.json 2> $O/bench_cfg4_nocentre_$rep.err
-PN_KNN_X3_P1=6 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_centre6_$rep.json 2> $O/bench_cfg4_centre6_$rep.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_centre_$rep.json 2> $O/bench_cfg4_centre_$rep.err
+PN_KNN_X3_CENTRE=0 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_nocentre_$rep.json 2> $O/bench_cfg4_nocentre_$rep.err
+PN_KNN_X3_P1=6 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_centre6_$rep.json 2> $O/bench_cfg4_centre6_$rep.err
 done
 for rep in 1 2; do
-timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_centre_$rep.json 2> $O/bench_cfg5_centre_$rep.err
-PN_KNN_X3_CENTRE=0 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_nocentre_$rep.json 2> $O/bench_cfg5_nocentre_$rep.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_centre_$rep.json 2> $O/bench_cfg5_centre_$rep.err
+PN_KNN_X3_CENTRE=0 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_nocentre_$rep.json 2> $O/bench_cfg5_nocentre_$rep.err
 done
 head -70 $O/copy_sites.txt | cut -c1-330; tail -12 $O/pytest.log; tail -6 $O/fuzz.log | cut -c1-300; head -4 $O/kbench_centre.log; head -4 $O/kbench_nocentre.log
 for f in $O/bench_*.json; do echo $f; python -c "

@@ -10,13 +10,13 @@ timeout 300 python tools/kbench.py knn > $O/kbench_p2_3.log 2>&1
 PN_KNN_X3_P2=6 timeout 300 python tools/kbench.py knn > $O/kbench_p2_6.log 2>&1
 export PARSENET_PRETRAIN_CACHE=/tmp/pre_h.pt
 for rep in 1 2; do
-timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p2three_$rep.json 2> $O/bench_cfg4_p2three_$rep.err
-PN_KNN_X3_P2=6 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p2six_$rep.json 2> $O/bench_cfg4_p2six_$rep.err
-PN_KNN_X3_CENTRE=0 timeout 600 python bench.py --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_r5form_$rep.json 2> $O/bench_cfg4_r5form_$rep.err
+timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p2three_$rep.json 2> $O/bench_cfg4_p2three_$rep.err
+PN_KNN_X3_P2=6 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_p2six_$rep.json 2> $O/bench_cfg4_p2six_$rep.err
+PN_KNN_X3_CENTRE=0 timeout 600 python bench.py --full --workload cfg4 --steps 30 --no-cpu-baseline > $O/bench_cfg4_r5form_$rep.json 2> $O/bench_cfg4_r5form_$rep.err
 done
 for rep in 1 2; do
-timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_p2three_$rep.json 2> $O/bench_cfg5_p2three_$rep.err
-PN_KNN_X3_P2=6 timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_p2six_$rep.json 2> $O/bench_cfg5_p2six_$rep.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_p2three_$rep.json 2> $O/bench_cfg5_p2three_$rep.err
+PN_KNN_X3_P2=6 timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_p2six_$rep.json 2> $O/bench_cfg5_p2six_$rep.err
 done
 tail -4 $O/pytest.log; tail -2 $O/fuzz.log | cut -c1-300; head -2 $O/kbench_p2_3.log | tail -1; head -2 $O/kbench_p2_6.log | tail -1
 for f in $O/bench_*.json; do echo $f; python -c "

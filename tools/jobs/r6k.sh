@@ -10,8 +10,8 @@ PN_CHAMFER_DIRECT_WGS=0 timeout 300 python tools/kbench.py chamfer > $O/kbench_s
 PN_CHAMFER_DIRECT_WGS=128 timeout 300 python tools/kbench.py chamfer > $O/kbench_direct128.log 2>&1
 timeout 600 python -m pytest tests/test_chamfer_gpu.py tests/test_fitting_batch_gpu.py tests/test_workloads_gpu.py -m gpu -q > $O/pytest.log 2>&1; echo "rc $?" >> $O/pytest.log
 for rep in 1 2; do
-timeout 600 python bench.py --workload cfg2 --no-cpu-baseline > $O/bench_cfg2_direct_$rep.json 2> $O/bench_cfg2_direct_$rep.err
-PN_CHAMFER_DIRECT_WGS=0 timeout 600 python bench.py --workload cfg2 --no-cpu-baseline > $O/bench_cfg2_split_$rep.json 2> $O/bench_cfg2_split_$rep.err
+timeout 600 python bench.py --full --workload cfg2 --no-cpu-baseline > $O/bench_cfg2_direct_$rep.json 2> $O/bench_cfg2_direct_$rep.err
+PN_CHAMFER_DIRECT_WGS=0 timeout 600 python bench.py --full --workload cfg2 --no-cpu-baseline > $O/bench_cfg2_split_$rep.json 2> $O/bench_cfg2_split_$rep.err
 done
 grep "scalar" $O/kbench_direct384.log | cut -c1-150; echo; grep "scalar" $O/kbench_split.log | cut -c1-150; echo; grep "scalar" $O/kbench_direct128.log | cut -c1-150
 tail -3 $O/pytest.log

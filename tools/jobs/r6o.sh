@@ -9,12 +9,12 @@ timeout 1500 python -m pytest tests/test_meanshift_gpu.py tests/test_norms_gpu.p
 timeout 1800 python -m pytest tests/test_golden_gpu.py tests/test_parity_fullsize_bwd_gpu.py tests/test_e2e_gpu.py tests/test_encoder_gpu.py tests/test_workloads_gpu.py tests/test_determinism_gpu.py -q -m gpu > $O/pytest_whole.log 2>&1; echo "rc $?" >> $O/pytest_whole.log
 timeout 600 python tools/probes/op_lines.py > $O/op_lines.txt 2> $O/op_lines.err
 for i in 1 2; do
-  timeout 900 python bench.py --workload cfg5 --no-cpu-baseline > $O/bench_cfg5_new_$i.json 2> $O/bench_cfg5_new_$i.err
+  timeout 900 python bench.py --full --workload cfg5 --no-cpu-baseline > $O/bench_cfg5_new_$i.json 2> $O/bench_cfg5_new_$i.err
   if [ -d _ab_prev ]; then
-    (cd _ab_prev && timeout 900 python bench.py --workload cfg5 --no-cpu-baseline > ../$O/bench_cfg5_prev_$i.json 2> ../$O/bench_cfg5_prev_$i.err)
+    (cd _ab_prev && timeout 900 python bench.py --full --workload cfg5 --no-cpu-baseline > ../$O/bench_cfg5_prev_$i.json 2> ../$O/bench_cfg5_prev_$i.err)
   fi
 done
-timeout 900 python bench.py --workload cfg4 --no-cpu-baseline > $O/bench_cfg4_new.json 2> $O/bench_cfg4_new.err
+timeout 900 python bench.py --full --workload cfg4 --no-cpu-baseline > $O/bench_cfg4_new.json 2> $O/bench_cfg4_new.err
 tail -3 $O/pytest_units.log; tail -4 $O/pytest_whole.log
 python - <<'PY'
 import json, glob

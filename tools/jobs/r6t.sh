@@ -9,8 +9,8 @@ for i in 1 2; do
   (cd _ab_prev && timeout 600 python tools/kbench.py knn64 > ../$O/kbench_prev_$i.log 2>&1)
 done
 for i in 1 2; do
-  timeout 600 python bench.py --workload cfg4 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_cfg4_new_$i.json 2> $O/bench_cfg4_new_$i.err
-  (cd _ab_prev && timeout 600 python bench.py --workload cfg4 --steps 30 --warmup 5 --no-cpu-baseline > ../$O/bench_cfg4_prev_$i.json 2> ../$O/bench_cfg4_prev_$i.err)
+  timeout 600 python bench.py --full --workload cfg4 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_cfg4_new_$i.json 2> $O/bench_cfg4_new_$i.err
+  (cd _ab_prev && timeout 600 python bench.py --full --workload cfg4 --steps 30 --warmup 5 --no-cpu-baseline > ../$O/bench_cfg4_prev_$i.json 2> ../$O/bench_cfg4_prev_$i.err)
 done
 grep -H "knn_final\|^knn B\|^dot_sel" $O/kbench_*.log | cut -c1-160
 python - <<'PY'

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6v; mkdir -p $O
 for i in 1 2; do
   for G in 256 512 1024; do
-    PN_MS_FLAT_G=$G timeout 900 python bench.py --no-cpu-baseline --no-dense > $O/bench_cfg5_g${G}_$i.json 2> $O/bench_cfg5_g${G}_$i.err
+    PN_MS_FLAT_G=$G timeout 900 python bench.py --full --no-cpu-baseline --no-dense > $O/bench_cfg5_g${G}_$i.json 2> $O/bench_cfg5_g${G}_$i.err
   done
 done
 python - <<'PY'
