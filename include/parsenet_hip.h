@@ -137,6 +137,27 @@ int pn_meanshift_x3_iter_bwd_f32(const float* gy, const float* y, const float* q
                                  void* img_q, void* img_gu, float* opart_q, float* opart_x, float* gq,
                                  float* gx, void* stream);
 
+/* ---- mean-shift at embedding widths D = 32 and 64 (csrc/meanshift_w.hip) -------------------
+ * The same iteration and its recompute backward in bf16 x 3 arithmetic, dense launches only, for
+ * narrower embeddings (rows narrower than 32 / 64 are zero-padded by the caller: zero columns are
+ * exact in every product and stay zero through the renormalisation).  All scratch lives in ONE
+ * caller-allocated workspace.
+ *   workspace : bytes needed for (B,N,D); backward != 0: for iter_bwd.  0 for an unsupported shape.
+ *   iter_fwd  : q (B,N,D) the current iterate, x (B,N,D) the data, bsq (B) -> y (B,N,D), rsum,
+ *               unorm (B,N), as pn_meanshift_iter_fwd_f32.
+ *   iter_bwd  : gy = dL/dy -> gq = dL/dq (overwritten), gx += the iteration's contribution to dL/dx.
+ *   reuse_image != 0: the workspace still holds the tile images of this x from an earlier call
+ *               (the iterations of one clustering call share x); 0: they are rebuilt first.
+ * No atomics: partial sums are combined in a fixed order, results are bit-reproducible. */
+size_t pn_meanshift_w_workspace(int B, int N, int D, int backward);
+int pn_meanshift_w_iter_fwd_f32(const float* q, const float* x, const float* bsq, int B, int N, int D,
+                                float* y, float* rsum, float* unorm, void* workspace,
+                                size_t workspace_bytes, int reuse_image, void* stream);
+int pn_meanshift_w_iter_bwd_f32(const float* gy, const float* y, const float* q, const float* x,
+                                const float* rsum, const float* unorm, const float* bsq, int B, int N,
+                                int D, float* gq, float* gx, void* workspace, size_t workspace_bytes,
+                                int reuse_image, void* stream);
+
 /* Block-sparse variant.  K_ij = exp((q_i . x_j - 1) / b^2) of src/mean_shift.py:58-64 decays fast
  * on a clustered embedding; the (32-row tile of q) x (32-row tile of x) pairs a plan skips are
  * chosen, from rigorous bounds on the tiles' bounding caps on the unit sphere, such that for EVERY

@@ -619,6 +619,98 @@ def meanshift_x3_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx, plan=N
     return gq
 
 
+class MeanShiftWWorkspace:
+    """The one scratch buffer of the width-32 / width-64 mean-shift kernels (csrc/meanshift_w.hip) for a
+    (B,N,D) problem, shared by the iterations of a call.  The buffer also holds the tile images of the data
+    ``x``; ``image_of`` remembers WHICH tensor they were built from (the tensor object itself, kept alive here so
+    that its address cannot be handed to another tensor, and its version counter), so that a later call with
+    the same, unmodified ``x`` skips that launch and a call with any other ``x`` — or the same one written to
+    in place since — rebuilds them.  ``reset()`` forgets them."""
+
+    def __init__(self, B, N, D, device, backward=False):
+        nbytes = int(_lib.load().pn_meanshift_w_workspace(B, N, D, int(bool(backward))))
+        if nbytes == 0:
+            raise ValueError("meanshift_w: no kernel for shape (%d,%d,%d) (width 32 or 64)" % (B, N, D))
+        self.B, self.N, self.D, self.backward = B, N, D, bool(backward)
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.image_of = None
+
+    def reset(self):
+        self.image_of = None
+
+    def holds_image_of(self, x):
+        return self.image_of is not None and self.image_of[0] is x and self.image_of[1] == x._version
+
+    def took_image_of(self, x):
+        self.image_of = (x, x._version)
+
+
+def _msw_rows(t, name, B, N, device):
+    """A per-row operand of the width kernels: contiguous fp32 (B,N) on the launch device."""
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, N) or not t.is_contiguous() or t.device != device:
+        raise ValueError("%s must be a contiguous float32 (%d,%d) tensor on %s" % (name, B, N, device))
+    return t
+
+
+def _msw_bsq(bsq, B, device):
+    if bsq.dtype != torch.float32 or bsq.numel() != B or bsq.dim() != 1 or bsq.device != device:
+        raise ValueError("bsq must be a float32 (%d,) tensor on %s" % (B, device))
+    return bsq.contiguous()
+
+
+def meanshift_w_iter_fwd(q, x, bsq, ws, out=None):
+    """One mean-shift iteration at width 32 or 64: q (B,N,D) the current iterate, x (B,N,D) the data, bsq
+    (B) squared bandwidths -> (y (B,N,D), rsum (B,N), unorm (B,N)), the triple meanshift_x3_iter_fwd
+    returns.  ``out``: contiguous fp32 tensors of those shapes to write into.  The tile images of ``x`` in the
+    workspace are reused when they were built from this very ``x`` (see MeanShiftWWorkspace), rebuilt otherwise."""
+    require_cuda(q, x, bsq)
+    q, x = _f32c(q, "q"), _f32c(x, "x")
+    B, N, D = x.shape
+    bsq = _msw_bsq(bsq, B, x.device)
+    if tuple(q.shape) != (B, N, D) or (ws.B, ws.N, ws.D, ws.backward) != (B, N, D, False):
+        raise ValueError("meanshift_w_iter_fwd: q, x (B,N,D) and a forward workspace of that shape")
+    if out is not None:
+        y, rsum, unorm = out
+        for t, shp in ((y, (B, N, D)), (rsum, (B, N)), (unorm, (B, N))):
+            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != q.device:
+                raise ValueError("meanshift_w_iter_fwd: out tensors must be contiguous fp32 of shapes (B,N,D), (B,N), (B,N)")
+    else:
+        y = torch.empty_like(q)
+        rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
+        unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    with _lib.on_device(q.device):
+        rc = _lib.load().pn_meanshift_w_iter_fwd_f32(ptr(q), ptr(x), ptr(bsq), B, N, D, ptr(y), ptr(rsum), ptr(unorm),
+                                                     ptr(ws.buf), ws.buf.numel(), int(ws.holds_image_of(x)),
+                                                     current_stream(q.device))
+    check(rc, "pn_meanshift_w_iter_fwd_f32")
+    ws.took_image_of(x)
+    return y, rsum, unorm
+
+
+def meanshift_w_iter_bwd(gy, y, q, x, rsum, unorm, bsq, ws, gx):
+    """Backward of that iteration (recomputes the kernel values): returns dL/dq, adds into ``gx``."""
+    require_cuda(gy, y, q, x, rsum, unorm, bsq, gx)
+    x = _f32c(x, "x")
+    B, N, D = x.shape
+    gy, y, q = _f32c(gy, "gy"), _f32c(y, "y"), _f32c(q, "q")
+    if not (tuple(gy.shape) == tuple(y.shape) == tuple(q.shape) == (B, N, D)):
+        raise ValueError("meanshift_w_iter_bwd: gy, y, q must be (B,N,D) like x")
+    rsum, unorm = _msw_rows(rsum, "rsum", B, N, x.device), _msw_rows(unorm, "unorm", B, N, x.device)
+    bsq = _msw_bsq(bsq, B, x.device)
+    if (ws.B, ws.N, ws.D, ws.backward) != (B, N, D, True) or tuple(gx.shape) != (B, N, D):
+        raise ValueError("meanshift_w_iter_bwd: x, gx (B,N,D) and a backward workspace of that shape")
+    if gx.dtype != torch.float32 or not gx.is_contiguous():
+        raise TypeError("meanshift_w_iter_bwd: gx must be contiguous fp32")
+    gq = torch.empty_like(x)
+    with _lib.on_device(x.device):
+        rc = _lib.load().pn_meanshift_w_iter_bwd_f32(ptr(gy), ptr(y), ptr(q), ptr(x), ptr(rsum), ptr(unorm), ptr(bsq),
+                                                     B, N, D, ptr(gq), ptr(gx), ptr(ws.buf), ws.buf.numel(),
+                                                     int(ws.holds_image_of(x)), current_stream(x.device))
+    check(rc, "pn_meanshift_w_iter_bwd_f32")
+    ws.took_image_of(x)
+    return gq
+
+
 def gemm_x3_weight_image(w, transposed=False):
     """Pre-split bf16 x 3 image of a weight w (M,K) for gemm_x3 (transposed: of w^T, for the gradient
     w.r.t. the activations).  Returns a uint8 tensor."""

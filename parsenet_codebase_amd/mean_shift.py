@@ -66,6 +66,33 @@ LAST_PLAN_STATS = None      # diagnostics of the most recent call (only filled w
 # The iterations hold points and final iterate in the locality order the exact pruning needs.
 WANT_NEAREST = False
 LAST_NEAREST = None
+# Embedding widths other than 128 (gaussian kernel).  Widths 32 and 64 have kernels of their own
+# (csrc/meanshift_w.hip: bf16 x 3 arithmetic, dense launches, recompute backward); every other width
+# D <= 128 is zero-padded to the next of 32 / 64 / 128 — zero columns are exact in every product and
+# stay zero through the renormalisation — and sliced on the way out.  The block-sparse plans, the
+# locality order and the centre-rows backward stay 128-only.  PARSENET_MS_NARROW: "native" (default) /
+# "pad128": every width below 128 zero-padded to 128 and run on the 128-wide path (the A/B of
+# tools/meanshift_width_ab.py, profiles/meanshift_width_ab.txt).  The narrow kernels are bf16 x 3 only:
+# with PARSENET_MS_ARITH = f32 / fp16x2 narrow widths are padded to 128 as well, so the arithmetic asked
+# for is the arithmetic that runs.  Like the 128-wide path, all of this takes float32 tensors on the GPU
+# only (the tensor expressions these widths ran before accepted any device and dtype; those remain for
+# widths above 128 and the Epanechnikov kernel).
+NARROW = os.environ.get("PARSENET_MS_NARROW", "native")
+NARROW_WIDTHS = (32, 64)
+CALLS_W = 0                 # calls of the iterations that ran on the width-32 / width-64 kernels
+
+
+def kernel_width(D):
+    """The width the iterations of a D-wide embedding run at (D zero-padded up to it), None above 128."""
+    if NARROW not in ("native", "pad128"):
+        raise ValueError("PARSENET_MS_NARROW must be native or pad128, not %r" % NARROW)
+    if D > 128:
+        return None
+    if NARROW == "native" and ARITH == "bf16x3":
+        for W in NARROW_WIDTHS:
+            if D <= W:
+                return W
+    return 128
 
 
 def use_sparse(B, N):
@@ -176,6 +203,13 @@ def _run_iterations(X, bsq, iterations, stacked=False, rel_eps=None):
     B, N, D = x.shape
     if ARITH not in _SPLIT and ARITH != "f32":
         raise ValueError("PARSENET_MS_ARITH must be fp16x2, bf16x3 or f32, not %r" % ARITH)
+    if D != 128:
+        # (rel_eps bounds what a block-sparse plan may drop: the width kernels launch dense and drop nothing)
+        if kernel_width(D) != D:
+            raise ValueError("_run_iterations: width %d does not run as it is with PARSENET_MS_NARROW=%s and "
+                             "PARSENET_MS_ARITH=%s; mean_shift_iterations zero-pads it to %s"
+                             % (D, NARROW, ARITH, kernel_width(D)))
+        return _run_iterations_w(x, bsq, iterations, stacked)
     kern = _SPLIT.get(ARITH) if iterations > 0 else None
     sparse = kern is not None and ARITH == "bf16x3" and SPARSE_MIN_N <= N <= SPARSE_MAX_N and use_sparse(B, N)
     if kern is not None and ARITH == "bf16x3":
@@ -239,6 +273,34 @@ def _run_iterations(X, bsq, iterations, stacked=False, rel_eps=None):
             "iterates_all": it_all, "rsums_all": rs_all, "norms_all": nr_all}
 
 
+def _run_iterations_w(x, bsq, iterations, stacked):
+    """``_run_iterations`` on the width-32 / width-64 kernels: dense launches in the given order, the same
+    dict (no tile images, no plans: ``x3`` / ``xt`` / ``perm`` / ``inv`` are None)."""
+    global CALLS_W, LAST_NEAREST
+    B, N, D = x.shape
+    LAST_NEAREST = None
+    CALLS_W += 1
+    it_all = rs_all = nr_all = None
+    if stacked:
+        it_all = torch.empty((iterations + 1, B, N, D), dtype=torch.float32, device=x.device)
+        rs_all = torch.empty((iterations, B, N), dtype=torch.float32, device=x.device)
+        nr_all = torch.empty((iterations, B, N), dtype=torch.float32, device=x.device)
+        it_all[0].copy_(x)
+        x = it_all[0]
+    ws = K.MeanShiftWWorkspace(B, N, D, x.device) if iterations > 0 else None
+    iterates, rsums, norms = [x], [], []
+    q = x
+    for it in range(iterations):
+        out = (it_all[it + 1], rs_all[it], nr_all[it]) if stacked else None
+        q, r, n = K.meanshift_w_iter_fwd(q, x, bsq, ws, out=out)
+        iterates.append(q)
+        rsums.append(r)
+        norms.append(n)
+    return {"x": x, "xt": None, "x3": None, "kern": "w", "sparse": False, "perm": None, "inv": None, "q": q,
+            "iterates": iterates, "rsums": rsums, "norms": norms, "plans": [],
+            "iterates_all": it_all, "rsums_all": rs_all, "norms_all": nr_all}
+
+
 class _MeanShiftIterations(torch.autograd.Function):
     """X (B,N,D) unit rows, bsq (B) squared bandwidths -> iterate after ``iterations`` steps.
     Saves only the iterates, row sums and norms (O(T N D)); the backward recomputes the kernel."""
@@ -252,6 +314,7 @@ class _MeanShiftIterations(torch.autograd.Function):
         ctx.x3 = st["x3"]
         ctx.kern = st["kern"]
         ctx.sparse = sparse
+        ctx.narrow = st["kern"] == "w"
         ctx.save_for_backward(st["xt"], bsq, *st["iterates"], *st["rsums"], *st["norms"], *st["plans"],
                               *([st["perm"], st["inv"]] if sparse else []))
         if iterations == 0:
@@ -269,9 +332,15 @@ class _MeanShiftIterations(torch.autograd.Function):
         plans = saved[3 + 3 * T:3 + 4 * T] if ctx.sparse else None
         x = iterates[0]
         B, N, D = x.shape
-        ws = K.MeanShiftWorkspace(B, N, D, x.device, backward=True, exact_f32=ctx.x3 is None)
         gX = torch.zeros_like(x)
         g = gy.contiguous()
+        if ctx.narrow:
+            ws = K.MeanShiftWWorkspace(B, N, D, x.device, backward=True) if T > 0 else None
+            for it in reversed(range(T)):
+                g = K.meanshift_w_iter_bwd(g, iterates[it + 1], iterates[it], x, rsums[it], norms[it], bsq, ws, gX)
+            gX += g  # the first iterate is X itself
+            return gX, None, None
+        ws = K.MeanShiftWorkspace(B, N, D, x.device, backward=True, exact_f32=ctx.x3 is None)
         if ctx.sparse:
             perm, inv = saved[-2], saved[-1]
             g = torch.gather(g, 1, perm.unsqueeze(2).expand(-1, -1, D))
@@ -291,16 +360,24 @@ class _MeanShiftIterations(torch.autograd.Function):
 
 
 def mean_shift_iterations(X, b, iterations):
-    """X (N,D) or (B,N,D); b scalar / 0-dim tensor / (B,) tensor of bandwidths."""
+    """X (N,D) or (B,N,D), D <= 128; b scalar / 0-dim tensor / (B,) tensor of bandwidths.  Widths without
+    kernels of their own run zero-padded to the next width that has them (``kernel_width``)."""
     require_cuda(X)
     squeeze = X.dim() == 2
     Xb = X.unsqueeze(0) if squeeze else X
-    B = Xb.shape[0]
+    B, D = Xb.shape[0], Xb.shape[2]
+    W = kernel_width(D)
+    if W is None:
+        raise ValueError("mean_shift_iterations: embedding width %d has no kernel (at most 128)" % D)
+    if W != D:
+        Xb = torch.nn.functional.pad(Xb, (0, W - D))
     bt = torch.as_tensor(b, dtype=torch.float32, device=X.device).reshape(-1)
     if bt.numel() == 1:
         bt = bt.expand(B)
     bsq = (bt.detach() ** 2).contiguous()
     out = _MeanShiftIterations.apply(Xb, bsq, int(iterations))
+    if W != D:
+        out = out[..., :D]
     return out[0] if squeeze else out
 
 
@@ -441,9 +518,9 @@ class MeanShift:
 
     # -- src/mean_shift.py:45-79 ---------------------------------------------------------
     def mean_shift_(self, X, b, iterations=10, kernel_type="gaussian"):
-        if kernel_type == "gaussian" and X.shape[-1] == 128:
+        if kernel_type == "gaussian" and kernel_width(X.shape[-1]) is not None:
             return mean_shift_iterations(X, b, iterations), X
-        # Epanechnikov kernel / other embedding sizes: never used by the training path; plain
+        # Epanechnikov kernel / embeddings wider than 128: never used by the training path; plain
         # tensor expressions on the GPU (materialises N x N like the reference)
         new_X = X.clone()
         for _ in range(iterations):

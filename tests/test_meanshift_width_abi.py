@@ -1,0 +1,81 @@
+"""CPU: the entry points of the width-32 / width-64 mean-shift kernels (csrc/meanshift_w.hip) are declared in
+include/parsenet_hip.h, exported by the built library and bound in the ctypes table — and the library refuses
+widths it has no kernel for instead of running something else."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "parsenet_hip.h")
+NAMES = ("pn_meanshift_w_workspace", "pn_meanshift_w_iter_fwd_f32", "pn_meanshift_w_iter_bwd_f32")
+
+
+@pytest.fixture(scope="module")
+def lib_path():
+    from parsenet_codebase_amd import build
+    return build.build(verbose=False)
+
+
+def test_header_declares_the_width_entry_points():
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = set(re.findall(r"\b(pn_[a-z0-9_]+)\s*\(", txt))
+    assert not [n for n in NAMES if n not in declared]
+
+
+def test_library_exports_and_ctypes_table_binds_them(lib_path):
+    from parsenet_codebase_amd import _lib
+    lib = ctypes.CDLL(lib_path)
+    assert not [n for n in NAMES if not hasattr(lib, n)]
+    assert not [n for n in NAMES if n not in _lib.SIGNATURES]
+
+
+def test_workspace_query_knows_its_widths(lib_path):
+    """Sizes are host arithmetic: positive for 32 and 64, growing with N, larger for the backward (two more
+    image arrays, the column pass's partial sums), and 0 — "no kernel" — for every other width."""
+    from parsenet_codebase_amd import _lib
+    lib = _lib.load()
+    for D in (32, 64):
+        f, b = lib.pn_meanshift_w_workspace(1, 10000, D, 0), lib.pn_meanshift_w_workspace(1, 10000, D, 1)
+        assert 0 < f < b
+        assert lib.pn_meanshift_w_workspace(1, 300, D, 0) < f
+        # far below one N x N fp32 matrix (4e8 bytes at N = 10 000): what the fused path is for
+        assert b < 4 * 10000 * 10000 // 2
+    for D in (0, 16, 50, 96, 128, 256):
+        assert lib.pn_meanshift_w_workspace(1, 10000, D, 0) == 0
+    assert lib.pn_meanshift_w_workspace(0, 10000, 64, 0) == 0
+
+
+def test_dispatch_table_of_the_widths(monkeypatch):
+    """mean_shift.kernel_width: 32 and 64 run natively, narrower rows are padded up to them, 65 ... 128 to 128,
+    nothing above; the switches (pad128, the non-default arithmetics) send every narrow width to 128."""
+    from parsenet_codebase_amd import mean_shift as MSM
+    monkeypatch.setattr(MSM, "NARROW", "native")
+    monkeypatch.setattr(MSM, "ARITH", "bf16x3")
+    assert [MSM.kernel_width(d) for d in (1, 20, 32, 33, 50, 64, 65, 96, 128, 129)] == \
+        [32, 32, 32, 64, 64, 64, 128, 128, 128, None]
+    monkeypatch.setattr(MSM, "NARROW", "pad128")
+    assert [MSM.kernel_width(d) for d in (20, 32, 64, 96, 128, 200)] == [128, 128, 128, 128, 128, None]
+    monkeypatch.setattr(MSM, "NARROW", "native")
+    monkeypatch.setattr(MSM, "ARITH", "f32")
+    assert [MSM.kernel_width(d) for d in (32, 64)] == [128, 128]
+
+
+def test_iterations_refuse_a_width_the_switches_send_elsewhere(monkeypatch):
+    """_run_iterations runs a width as it is: 64-wide rows under pad128 or the f32 arithmetic must not end on
+    the bf16 x 3 width kernels behind the caller's back (mean_shift_iterations pads them to 128 first)."""
+    import torch
+    from parsenet_codebase_amd import mean_shift as MSM
+    x, bsq = torch.zeros(1, 40, 64), torch.ones(1)
+    monkeypatch.setattr(MSM, "ARITH", "bf16x3")
+    monkeypatch.setattr(MSM, "NARROW", "pad128")
+    with pytest.raises(ValueError, match="pad128"):
+        MSM._run_iterations(x, bsq, 1)
+    monkeypatch.setattr(MSM, "NARROW", "native")
+    monkeypatch.setattr(MSM, "ARITH", "f32")
+    with pytest.raises(ValueError, match="f32"):
+        MSM._run_iterations(x, bsq, 1)
+    monkeypatch.setattr(MSM, "ARITH", "bf16x3")
+    with pytest.raises(ValueError):
+        MSM._run_iterations(torch.zeros(1, 40, 50), bsq, 1)
