@@ -158,6 +158,35 @@ int pn_meanshift_w_iter_bwd_f32(const float* gy, const float* y, const float* q,
                                 int D, float* gq, float* gx, void* workspace, size_t workspace_bytes,
                                 int reuse_image, void* stream);
 
+/* ---- mean-shift with the kernel profile as an argument ---------------------------------------
+ * The entry points above with one more argument, `kind` (before `stream`): the kernel_type of
+ * src/mean_shift.py:45-79.  The two profiles differ in the elementwise stage between the two GEMMs
+ * of a tile pair only; images, workspaces, scratch sizes, slices and outputs are the same.
+ *   PN_MS_KERNEL_GAUSSIAN      K = exp(clamp(-(2 - 2 q x^T) / b^2 / 2, -75, 75)): exactly the calls above.
+ *   PN_MS_KERNEL_EPANECHNIKOV  K = max(0, 3/4 (1 - (2 - 2 q x^T) / b^2)) (src/mean_shift.py:64-68); in the
+ *                              backward dK is 3/2 / b^2 on the support and 0 off it.  A row without
+ *                              support has row sum 0 and comes out non-finite, as in the reference.
+ * The 128-wide calls take the `plan` of the _plan_ variants; block-sparse plans bound the tail of the
+ * exponential, so a call with kind != PN_MS_KERNEL_GAUSSIAN and plan != NULL is refused
+ * (PN_ERR_UNSUPPORTED, nothing is launched).  Any other kind: PN_ERR_ARG. */
+#define PN_MS_KERNEL_GAUSSIAN 0
+#define PN_MS_KERNEL_EPANECHNIKOV 1
+int pn_meanshift_w_iter_fwd_kind_f32(const float* q, const float* x, const float* bsq, int B, int N, int D,
+                                     float* y, float* rsum, float* unorm, void* workspace,
+                                     size_t workspace_bytes, int reuse_image, int kind, void* stream);
+int pn_meanshift_w_iter_bwd_kind_f32(const float* gy, const float* y, const float* q, const float* x,
+                                     const float* rsum, const float* unorm, const float* bsq, int B, int N,
+                                     int D, float* gq, float* gx, void* workspace, size_t workspace_bytes,
+                                     int reuse_image, int kind, void* stream);
+int pn_meanshift_x3_iter_fwd_kind_f32(const float* q, const void* img_x, const float* bsq, int B, int N,
+                                      int D, float* opart, float* rpart, float* y, float* rsum,
+                                      float* unorm, const void* plan, int kind, void* stream);
+int pn_meanshift_x3_iter_bwd_kind_f32(const float* gy, const float* y, const float* q, const float* x,
+                                      const void* img_x, const float* rsum, const float* unorm,
+                                      const float* bsq, int B, int N, int D, float* gu, float* cs,
+                                      void* img_q, void* img_gu, float* opart_q, float* opart_x, float* gq,
+                                      float* gx, const void* plan, int kind, void* stream);
+
 /* Block-sparse variant.  K_ij = exp((q_i . x_j - 1) / b^2) of src/mean_shift.py:58-64 decays fast
  * on a clustered embedding; the (32-row tile of q) x (32-row tile of x) pairs a plan skips are
  * chosen, from rigorous bounds on the tiles' bounding caps on the unit sphere, such that for EVERY

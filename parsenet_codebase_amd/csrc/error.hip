@@ -16,4 +16,5 @@ extern "C" const char* pn_last_error(void) { return g_err; }
 // 2: edge-conv backward takes a workspace, mean-shift backward reduces its partial sums itself,
 //    bf16 x 3 mean-shift entry points
 // 19: mean-shift at embedding widths 32 and 64 (pn_meanshift_w_*)
-extern "C" int pn_abi_version(void) { return 19; }
+// 20: the kernel profile as an argument (pn_meanshift_*_iter_*_kind_f32: Gaussian / Epanechnikov)
+extern "C" int pn_abi_version(void) { return 20; }

@@ -28,6 +28,14 @@
 // Partial results of the column slices are combined in slice order by separate launches: no
 // floating-point atomics, bit-identical results from run to run.  Rows >= N of a tail tile are zero
 // image rows (they add nothing in the second GEMM) and their K is masked out of the row sums.
+//
+// KIND (compile time) selects the kernel profile of the elementwise stage between the two GEMMs:
+//   MSW_GAUSS  the above;
+//   MSW_EPA    Epanechnikov: with dist_ij = 2 - 2 q_i . x_j, K_ij = max(0, 0.75 (1 - dist_ij / b^2)), no clamp,
+//              and, dK/d(q.x) being 1.5 / b^2 on the support and 0 off it,
+//              gs_ij = K_ij > 0 ? 1.5 (gu_i . x_j - c_i) alpha_i : 0.
+// Everything else (r, u, n, y, gu, c, alpha, the K / r_i weight of the GU term, images, slices, combines)
+// is shared.  A row without support has r_i = 0 and comes out non-finite, as in the reference.
 #include "split_common.h"
 
 #define MSW_LOG2E 1.4426950408889634f
@@ -36,6 +44,8 @@
 #define MSW_THREADS (64 * MSW_WAVES)
 #define MSW_ROWS (32 * MSW_WAVES)       // resident rows of a workgroup
 #define MSW_MAX_SLICES 8
+#define MSW_GAUSS 0
+#define MSW_EPA 1
 
 typedef float mswf16 __attribute__((ext_vector_type(16)));
 
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(256) void pn_msw_prologue_bwd_kernel(
 // PA, PB  tile images of the streamed operand(s) (PB: GU, PASS 2 only)
 // cs, rs  per-row c_i and alpha_i: of the resident row (PASS 1) / of the streamed rows (PASS 2)
 // grid (slices, blocks of 256 resident indices, B), 512 threads: wave w owns rows 32 w .. 32 w + 31.
-template <int W, int PASS>
+template <int W, int PASS, int KIND>
 __global__ __launch_bounds__(MSW_THREADS) void pn_msw_kernel(
     const float* __restrict__ R, const float* __restrict__ R1, const u32x4* __restrict__ PA,
     const u32x4* __restrict__ PB, const float* __restrict__ cs, const float* __restrict__ rs,
@@ -175,6 +185,7 @@ __global__ __launch_bounds__(MSW_THREADS) void pn_msw_kernel(
   const bool wave_on = i0 < N;
   const float bsqv = bsq_[b];
   const float hl = (0.5f / bsqv) * MSW_LOG2E;
+  const float ib = 1.0f / bsqv;   // (MSW_EPA)
   const size_t bN = (size_t)b * N;
   const u32x4* __restrict__ PAb = PA + (size_t)b * ntiles * IMG;
   const u32x4* __restrict__ PBb = PASS == 2 ? PB + (size_t)b * ntiles * IMG : nullptr;
@@ -313,9 +324,14 @@ __global__ __launch_bounds__(MSW_THREADS) void pn_msw_kernel(
       for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
         const float dist = __builtin_fmaf(-2.0f, sa[r], 2.0f);
-        const float a2 = -dist * hl;
-        const float a2c = __builtin_amdgcn_fmed3f(a2, -MSW_LIM2, MSW_LIM2);
-        float k = __builtin_amdgcn_exp2f(a2c);
+        float k, a2 = 0.f, a2c = 0.f;
+        if constexpr (KIND == MSW_EPA) {
+          k = fmaxf(0.0f, 0.75f * __builtin_fmaf(-dist, ib, 1.0f));
+        } else {
+          a2 = -dist * hl;
+          a2c = __builtin_amdgcn_fmed3f(a2, -MSW_LIM2, MSW_LIM2);
+          k = __builtin_amdgcn_exp2f(a2c);
+        }
         if (PASS == 0) {
           // padded points have all-zero image rows: they add nothing in the second GEMM whatever
           // their weight, so only the row sums need the mask
@@ -325,8 +341,13 @@ __global__ __launch_bounds__(MSW_THREADS) void pn_msw_kernel(
         } else {
           const float cc = PASS == 1 ? c_res : lds_sc[cur][row];
           const float aa = PASS == 1 ? a_res : lds_sc[cur][32 + row];
-          const float g = k * ((ta[r] - cc) * aa);
-          gs[PASS == 0 ? 0 : r] = a2c == a2 ? g : 0.f;
+          if constexpr (KIND == MSW_EPA) {   // dK/d(q.x) = 1.5 / b^2 on the support, 0 off it
+            const float g = 1.5f * ((ta[r] - cc) * aa);
+            gs[PASS == 0 ? 0 : r] = k > 0.0f ? g : 0.f;
+          } else {
+            const float g = k * ((ta[r] - cc) * aa);
+            gs[PASS == 0 ? 0 : r] = a2c == a2 ? g : 0.f;
+          }
           kv[r] = PASS == 2 ? k * (aa * bsqv) : k;   // weight of the GU term: K / r_i
         }
       }
@@ -506,7 +527,7 @@ extern "C" size_t pn_meanshift_w_workspace(int B, int N, int D, int backward) {
   return msw_layout(B, N, D, backward).total;
 }
 
-template <int W>
+template <int W, int KIND>
 static int msw_fwd(const float* q, const float* x, const float* bsq, int B, int N, float* y, float* rsum,
                    float* unorm, char* ws, int reuse_image, hipStream_t stream) {
   const MswLayout L = msw_layout(B, N, W, 0);
@@ -519,7 +540,7 @@ static int msw_fwd(const float* q, const float* x, const float* bsq, int B, int 
   }
   {
     PN_PROF("meanshift_w_fwd", stream);
-    hipLaunchKernelGGL((pn_msw_kernel<W, 0>), dim3(L.S, pn_cdiv(N, MSW_ROWS), B), dim3(MSW_THREADS), 0, stream, q,
+    hipLaunchKernelGGL((pn_msw_kernel<W, 0, KIND>), dim3(L.S, pn_cdiv(N, MSW_ROWS), B), dim3(MSW_THREADS), 0, stream, q,
                        (const float*)nullptr, (const u32x4*)img_x, (const u32x4*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, bsq, N, L.ntiles, L.tps, opart, rpart);
   }
@@ -530,7 +551,7 @@ static int msw_fwd(const float* q, const float* x, const float* bsq, int B, int 
   return PN_OK;
 }
 
-template <int W>
+template <int W, int KIND>
 static int msw_bwd(const float* gy, const float* y, const float* q, const float* x, const float* rsum,
                    const float* unorm, const float* bsq, int B, int N, float* gq, float* gx, char* ws,
                    int reuse_image, hipStream_t stream) {
@@ -553,14 +574,14 @@ static int msw_bwd(const float* gy, const float* y, const float* q, const float*
   const dim3 grid(L.S, pn_cdiv(N, MSW_ROWS), B);
   {
     PN_PROF("meanshift_w_bwd_rows", stream);
-    hipLaunchKernelGGL((pn_msw_kernel<W, 1>), grid, dim3(MSW_THREADS), 0, stream, q, (const float*)gu,
+    hipLaunchKernelGGL((pn_msw_kernel<W, 1, KIND>), grid, dim3(MSW_THREADS), 0, stream, q, (const float*)gu,
                        (const u32x4*)img_x, (const u32x4*)nullptr, (const float*)cs, (const float*)alpha, bsq, N,
                        L.ntiles, L.tps, opart_q, (float*)nullptr);
   }
   PN_CHECK_LAUNCH();
   {
     PN_PROF("meanshift_w_bwd_cols", stream);
-    hipLaunchKernelGGL((pn_msw_kernel<W, 2>), grid, dim3(MSW_THREADS), 0, stream, x, (const float*)nullptr,
+    hipLaunchKernelGGL((pn_msw_kernel<W, 2, KIND>), grid, dim3(MSW_THREADS), 0, stream, x, (const float*)nullptr,
                        (const u32x4*)img_q, (const u32x4*)img_gu, (const float*)cs, (const float*)alpha, bsq, N,
                        L.ntiles, L.tps, opart_x, (float*)nullptr);
   }
@@ -572,45 +593,72 @@ static int msw_bwd(const float* gy, const float* y, const float* q, const float*
   return PN_OK;
 }
 
+static bool msw_kind_ok(int kind) { return kind == MSW_GAUSS || kind == MSW_EPA; }
+
 // One forward iteration at D = 32 or 64.  q, x (B,N,D) (q: the current iterate, x: the data), bsq (B);
 // writes y (B,N,D), rsum, unorm (B,N).  workspace: pn_meanshift_w_workspace(B, N, D, 0) bytes;
 // reuse_image != 0: it already holds the tile images of this x (an earlier call with the same
-// workspace, i.e. the previous iteration of the same clustering call).
-extern "C" int pn_meanshift_w_iter_fwd_f32(const float* q, const float* x, const float* bsq, int B, int N, int D,
-                                           float* y, float* rsum, float* unorm, void* workspace,
-                                           size_t workspace_bytes, int reuse_image, void* stream) {
-  PN_CHECK_ARG(q && x && bsq && y && rsum && unorm && workspace, "pn_meanshift_w_iter_fwd_f32: null pointer");
-  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_w_iter_fwd_f32: empty input");
+// workspace, i.e. the previous iteration of the same clustering call).  kind: the kernel profile,
+// 0 Gaussian / 1 Epanechnikov (the images and the workspace do not depend on it).
+extern "C" int pn_meanshift_w_iter_fwd_kind_f32(const float* q, const float* x, const float* bsq, int B, int N,
+                                                int D, float* y, float* rsum, float* unorm, void* workspace,
+                                                size_t workspace_bytes, int reuse_image, int kind, void* stream) {
+  PN_CHECK_ARG(q && x && bsq && y && rsum && unorm && workspace, "pn_meanshift_w_iter_fwd: null pointer");
+  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_w_iter_fwd: empty input");
   PN_CHECK_ARG(msw_width_ok(D), "pn_meanshift_w: embedding size %d unsupported (32 or 64; pad narrower rows with zeros)", D);
+  PN_CHECK_ARG(msw_kind_ok(kind), "pn_meanshift_w: kernel kind %d unknown (0 Gaussian, 1 Epanechnikov)", kind);
   if (workspace_bytes < pn_meanshift_w_workspace(B, N, D, 0)) {
-    pn_set_error("pn_meanshift_w_iter_fwd_f32: workspace of %zu bytes, %zu needed", workspace_bytes,
+    pn_set_error("pn_meanshift_w_iter_fwd: workspace of %zu bytes, %zu needed", workspace_bytes,
                  pn_meanshift_w_workspace(B, N, D, 0));
     return PN_ERR_WORKSPACE;
   }
-  if (D == 32)
-    return msw_fwd<32>(q, x, bsq, B, N, y, rsum, unorm, (char*)workspace, reuse_image, (hipStream_t)stream);
-  return msw_fwd<64>(q, x, bsq, B, N, y, rsum, unorm, (char*)workspace, reuse_image, (hipStream_t)stream);
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == MSW_EPA)
+    return D == 32 ? msw_fwd<32, MSW_EPA>(q, x, bsq, B, N, y, rsum, unorm, ws, reuse_image, st)
+                   : msw_fwd<64, MSW_EPA>(q, x, bsq, B, N, y, rsum, unorm, ws, reuse_image, st);
+  return D == 32 ? msw_fwd<32, MSW_GAUSS>(q, x, bsq, B, N, y, rsum, unorm, ws, reuse_image, st)
+                 : msw_fwd<64, MSW_GAUSS>(q, x, bsq, B, N, y, rsum, unorm, ws, reuse_image, st);
+}
+
+// ... with the Gaussian kernel
+extern "C" int pn_meanshift_w_iter_fwd_f32(const float* q, const float* x, const float* bsq, int B, int N, int D,
+                                           float* y, float* rsum, float* unorm, void* workspace,
+                                           size_t workspace_bytes, int reuse_image, void* stream) {
+  return pn_meanshift_w_iter_fwd_kind_f32(q, x, bsq, B, N, D, y, rsum, unorm, workspace, workspace_bytes,
+                                          reuse_image, MSW_GAUSS, stream);
 }
 
 // Backward of that iteration (recomputes K): gy = dL/dy, (y, rsum, unorm) the iteration's saved
 // outputs, q its input iterate.  Writes gq = dL/dq (B,N,D) and ADDS the iteration's contribution to
-// dL/dx into gx.  workspace: pn_meanshift_w_workspace(B, N, D, 1) bytes; reuse_image as above.
+// dL/dx into gx.  workspace: pn_meanshift_w_workspace(B, N, D, 1) bytes; reuse_image, kind as above.
+extern "C" int pn_meanshift_w_iter_bwd_kind_f32(const float* gy, const float* y, const float* q, const float* x,
+                                                const float* rsum, const float* unorm, const float* bsq, int B,
+                                                int N, int D, float* gq, float* gx, void* workspace,
+                                                size_t workspace_bytes, int reuse_image, int kind, void* stream) {
+  PN_CHECK_ARG(gy && y && q && x && rsum && unorm && bsq && gq && gx && workspace,
+               "pn_meanshift_w_iter_bwd: null pointer");
+  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_w_iter_bwd: empty input");
+  PN_CHECK_ARG(msw_width_ok(D), "pn_meanshift_w: embedding size %d unsupported (32 or 64; pad narrower rows with zeros)", D);
+  PN_CHECK_ARG(msw_kind_ok(kind), "pn_meanshift_w: kernel kind %d unknown (0 Gaussian, 1 Epanechnikov)", kind);
+  if (workspace_bytes < pn_meanshift_w_workspace(B, N, D, 1)) {
+    pn_set_error("pn_meanshift_w_iter_bwd: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 pn_meanshift_w_workspace(B, N, D, 1));
+    return PN_ERR_WORKSPACE;
+  }
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == MSW_EPA)
+    return D == 32 ? msw_bwd<32, MSW_EPA>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, ws, reuse_image, st)
+                   : msw_bwd<64, MSW_EPA>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, ws, reuse_image, st);
+  return D == 32 ? msw_bwd<32, MSW_GAUSS>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, ws, reuse_image, st)
+                 : msw_bwd<64, MSW_GAUSS>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, ws, reuse_image, st);
+}
+
 extern "C" int pn_meanshift_w_iter_bwd_f32(const float* gy, const float* y, const float* q, const float* x,
                                            const float* rsum, const float* unorm, const float* bsq, int B, int N,
                                            int D, float* gq, float* gx, void* workspace, size_t workspace_bytes,
                                            int reuse_image, void* stream) {
-  PN_CHECK_ARG(gy && y && q && x && rsum && unorm && bsq && gq && gx && workspace,
-               "pn_meanshift_w_iter_bwd_f32: null pointer");
-  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_w_iter_bwd_f32: empty input");
-  PN_CHECK_ARG(msw_width_ok(D), "pn_meanshift_w: embedding size %d unsupported (32 or 64; pad narrower rows with zeros)", D);
-  if (workspace_bytes < pn_meanshift_w_workspace(B, N, D, 1)) {
-    pn_set_error("pn_meanshift_w_iter_bwd_f32: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 pn_meanshift_w_workspace(B, N, D, 1));
-    return PN_ERR_WORKSPACE;
-  }
-  if (D == 32)
-    return msw_bwd<32>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, (char*)workspace, reuse_image,
-                       (hipStream_t)stream);
-  return msw_bwd<64>(gy, y, q, x, rsum, unorm, bsq, B, N, gq, gx, (char*)workspace, reuse_image,
-                     (hipStream_t)stream);
+  return pn_meanshift_w_iter_bwd_kind_f32(gy, y, q, x, rsum, unorm, bsq, B, N, D, gq, gx, workspace,
+                                          workspace_bytes, reuse_image, MSW_GAUSS, stream);
 }

@@ -27,11 +27,22 @@
 // points (e&3) + 8(2t + (e>>2)) + 4h).  The swizzle makes both access patterns bank-conflict
 // free (16-lane service groups of ds_read_b128; 4 rows x 4 chunks of the transpose read).
 // (included at the end of meanshift.hip: one translation unit, shared combine kernels)
+//
+// KIND (compile time) selects the kernel profile, i.e. the elementwise stage between the two GEMMs:
+//   X3_GAUSS  K_ij = exp(clamp((q_i . x_j - 1) / b^2)), gs_ij = K_ij (gu_i . x_j - c_i) alpha_i;
+//   X3_EPA    Epanechnikov (src/mean_shift.py:64-68): with dist_ij = 2 - 2 q_i . x_j,
+//             K_ij = max(0, 0.75 (1 - dist_ij / b^2)), no clamp; dK/d(q.x) is 1.5 / b^2 on the support and 0
+//             off it: gs_ij = K_ij > 0 ? 1.5 (gu_i . x_j - c_i) alpha_i : 0.  Dense launches only: the plans'
+//             bounds are those of the exponential.  A row without support has r_i = 0 and comes out
+//             non-finite, as in the reference.
+// Row sums, u, n, y, gu, c, alpha, the K / r_i weight of the GU term, images, slices and combines are shared.
 
 #include "split_common.h"
 
 #define X3_IMG_U4 1536            // uint4 (16 B) units per 24 KiB tile image
 #define X3_PIECE_U4 512           // per piece
+#define X3_GAUSS 0
+#define X3_EPA 1
 
 // x (B,N,D) fp32 -> the image of every 32-point tile (rows >= N are zero).
 // One workgroup per tile; work item = one 16-byte chunk.
@@ -218,7 +229,7 @@ __device__ static inline int x3_cflag(const unsigned char* p) {   // one byte vi
 // SQ_VALU_MFMA_BUSY_CYCLES / 32 x 32 768 FLOP of a counter run reproduces it.
 __device__ unsigned long long pn_ms3_exec[3];
 
-template <int PASS, int MODE>
+template <int PASS, int MODE, int KIND>
 __global__ __launch_bounds__(64 * X3_WAVES(PASS))
 __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 1 : 2, PASS == 1 ? 1 : 2))) void pn_ms3_kernel(
     const float* __restrict__ R, const float* __restrict__ R1, const u32x4* __restrict__ PA,
@@ -314,6 +325,7 @@ __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 1 : 2, PASS == 1 ? 1 : 2))) void 
   }
   const float bsqv = bsq_[b];
   const float hl = (0.5f / bsqv) * MS_LOG2E;
+  const float ib = 1.0f / bsqv;   // (X3_EPA)
   const size_t bN = (size_t)b * N;
   const size_t boff = (size_t)b * ntiles * X3_IMG_U4;
   const u32x4* __restrict__ PAb = PA + boff;
@@ -576,10 +588,15 @@ __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 1 : 2, PASS == 1 ? 1 : 2))) void 
     const int row = ((R) & 3) + 8 * ((R) >> 2) + 4 * h;                            \
     const float sv = sa[R];                                                        \
     const float dist = __builtin_fmaf(-2.0f, sv, 2.0f);                            \
-    float a2 = -dist * hl;                                                         \
-    if (PASS == 2 && !X3_PACKED) asm("" : "+v"(a2));   /* no v_pk_mul_f32 beside the sibling's MFMAs */ \
-    const float a2c = __builtin_amdgcn_fmed3f(a2, -MS_LIM2, MS_LIM2);              \
-    float k = __builtin_amdgcn_exp2f(a2c);                                         \
+    float a2 = 0.f, a2c = 0.f, k;                                                  \
+    if constexpr (KIND == X3_EPA) {                                                \
+      k = __builtin_fmaxf(0.0f, 0.75f * __builtin_fmaf(-dist, ib, 1.0f));          \
+    } else {                                                                       \
+      a2 = -dist * hl;                                                             \
+      if (PASS == 2 && !X3_PACKED) asm("" : "+v"(a2));   /* no v_pk_mul_f32 beside the sibling's MFMAs */ \
+      a2c = __builtin_amdgcn_fmed3f(a2, -MS_LIM2, MS_LIM2);                        \
+      k = __builtin_amdgcn_exp2f(a2c);                                             \
+    }                                                                              \
     /* padded points have all-zero image rows: they add nothing in the second GEMM whatever \
        their weight, so only the row sums of the forward pass need the mask */          \
     if (PASS == 0 && (MASKED) && j0 + row >= N) k = 0.f;                           \
@@ -598,9 +615,9 @@ __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 1 : 2, PASS == 1 ? 1 : 2))) void 
       }                                                                            \
       float d_ = (tv - cc) * aa;                                                   \
       if (PASS == 2 && !X3_PACKED) asm("" : "+v"(d_));                             \
-      float g = k * d_;                                                            \
+      float g = KIND == X3_EPA ? 1.5f * d_ : k * d_;   /* dK/d(q.x) b^2 = 1.5 on the support | K */ \
       asm("" : "+v"(g));          /* keep the select a v_cndmask, not a branch */  \
-      gs[PASS == 0 ? 0 : (R)] = a2c == a2 ? g : 0.f;                               \
+      gs[PASS == 0 ? 0 : (R)] = (KIND == X3_EPA ? k > 0.0f : a2c == a2) ? g : 0.f; \
     }                                                                              \
   }
 #define X3_EW(R) X3_EW_(R, false)
@@ -1760,12 +1777,29 @@ static int x3_pingpong() {
   }
   return v;
 }
-#define X3_LAUNCH_PP(PASS, GRID, BLOCK, STREAM, ...)                                                  \
+#define X3_LAUNCH_PPK(PASS, KIND, GRID, BLOCK, STREAM, ...)                                           \
   {                                                                                                   \
     if (x3_pingpong() >= ((PASS) == 0 ? 2 : 1))                                                       \
-      hipLaunchKernelGGL((pn_ms3_kernel<PASS, 1>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);              \
+      hipLaunchKernelGGL((pn_ms3_kernel<PASS, 1, KIND>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);        \
     else                                                                                              \
-      hipLaunchKernelGGL((pn_ms3_kernel<PASS, 0>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);              \
+      hipLaunchKernelGGL((pn_ms3_kernel<PASS, 0, KIND>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);        \
+  }
+#define X3_LAUNCH_PP(PASS, GRID, BLOCK, STREAM, ...) X3_LAUNCH_PPK(PASS, X3_GAUSS, GRID, BLOCK, STREAM, __VA_ARGS__)
+// dense launches: the kernel profile is a run-time argument of the entry points
+#define X3_LAUNCH_KIND(PASS, KIND_, GRID, BLOCK, STREAM, ...)                  \
+  {                                                                            \
+    if ((KIND_) == X3_EPA) X3_LAUNCH_PPK(PASS, X3_EPA, GRID, BLOCK, STREAM, __VA_ARGS__) \
+    else X3_LAUNCH_PPK(PASS, X3_GAUSS, GRID, BLOCK, STREAM, __VA_ARGS__)       \
+  }
+// Epanechnikov launches are dense: a plan drops what the exponential's bounds allow
+#define X3_CHECK_KIND(KIND_, PLAN_, WHO)                                                                \
+  {                                                                                                     \
+    PN_CHECK_ARG((KIND_) == X3_GAUSS || (KIND_) == X3_EPA, WHO ": kernel kind %d unknown (0 Gaussian, 1 Epanechnikov)", \
+                 (int)(KIND_));                                                                         \
+    if ((KIND_) != X3_GAUSS && (PLAN_) != nullptr) {                                                    \
+      pn_set_error(WHO ": block-sparse plans are built for the Gaussian kernel; launch the Epanechnikov kernel dense (plan = NULL)"); \
+      return PN_ERR_UNSUPPORTED;                                                                        \
+    }                                                                                                   \
   }
 
 // Flat launches (block-sparse plan): one workgroup per CU, a multiple of the 8 XCDs.
@@ -1833,16 +1867,16 @@ extern "C" int pn_meanshift_x3_iter_fwd_plan_f32(const float* q, const void* img
 // ... and, when cen / rho are given, the bounding caps of the result's tiles (pn_meanshift_x3_tileinfo_f32 of y:
 // cen (B,ntiles,2,D), rho (B,ntiles,2), cnt (B,ntiles,2) or NULL) — what the plan of the NEXT iteration takes as
 // its q caps; with a plan they come out of the launch that combines the partial results.
-extern "C" int pn_meanshift_x3_iter_fwd_info_f32(const float* q, const void* img_x, const float* bsq, int B,
-                                                 int N, int D, float* opart, float* rpart, float* y,
-                                                 float* rsum, float* unorm, const void* plan, float* cen,
-                                                 float* rho, float* cnt, void* stream_) {
+static int x3_iter_fwd(const float* q, const void* img_x, const float* bsq, int B, int N, int D, float* opart,
+                       float* rpart, float* y, float* rsum, float* unorm, const void* plan, float* cen, float* rho,
+                       float* cnt, int kind, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  PN_CHECK_ARG((cen == nullptr) == (rho == nullptr), "pn_meanshift_x3_iter_fwd_info_f32: cen and rho go together");
+  X3_CHECK_KIND(kind, plan, "pn_meanshift_x3_iter_fwd");
+  PN_CHECK_ARG((cen == nullptr) == (rho == nullptr), "pn_meanshift_x3_iter_fwd: cen and rho go together");
   PN_CHECK_ARG(q && img_x && bsq && opart && rpart && y && rsum && unorm,
-               "pn_meanshift_x3_iter_fwd_f32: null pointer");
+               "pn_meanshift_x3_iter_fwd: null pointer");
   PN_CHECK_ARG(D == MS_D, "pn_meanshift: embedding size %d unsupported (built for %d)", D, MS_D);
-  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_x3_iter_fwd_f32: empty input");
+  PN_CHECK_ARG(B > 0 && N > 0, "pn_meanshift_x3_iter_fwd: empty input");
   const int ntiles = (int)pn_align_up(N, 64) / 32;
   const X3Plan pv = x3_plan_view(plan, B, N, ntiles);
   if (pv.flat) {
@@ -1871,7 +1905,7 @@ extern "C" int pn_meanshift_x3_iter_fwd_info_f32(const float* q, const void* img
   dim3 grid(S, pn_cdiv(N, 256), B);
   {
     PN_PROF("meanshift_fwd", stream);
-    X3_LAUNCH_PP(0, grid, dim3(512), stream, q, nullptr, (const u32x4*)img_x,
+    X3_LAUNCH_KIND(0, kind, grid, dim3(512), stream, q, nullptr, (const u32x4*)img_x,
                        nullptr, nullptr, nullptr, bsq, N, ntiles, tps, opart, rpart, nullptr, nullptr, nullptr,
                        nullptr, 0, 0, 0, 0, 0, 0);
   }
@@ -1884,6 +1918,23 @@ extern "C" int pn_meanshift_x3_iter_fwd_info_f32(const float* q, const void* img
     PN_CHECK_LAUNCH();
   }
   return PN_OK;
+}
+
+extern "C" int pn_meanshift_x3_iter_fwd_info_f32(const float* q, const void* img_x, const float* bsq, int B,
+                                                 int N, int D, float* opart, float* rpart, float* y,
+                                                 float* rsum, float* unorm, const void* plan, float* cen,
+                                                 float* rho, float* cnt, void* stream_) {
+  return x3_iter_fwd(q, img_x, bsq, B, N, D, opart, rpart, y, rsum, unorm, plan, cen, rho, cnt, X3_GAUSS, stream_);
+}
+
+// pn_meanshift_x3_iter_fwd_plan_f32 with the kernel profile as an argument: kind 0 Gaussian / 1 Epanechnikov.
+// The Epanechnikov kernel launches dense: with a plan the call is refused (PN_ERR_UNSUPPORTED).
+extern "C" int pn_meanshift_x3_iter_fwd_kind_f32(const float* q, const void* img_x, const float* bsq, int B,
+                                                 int N, int D, float* opart, float* rpart, float* y,
+                                                 float* rsum, float* unorm, const void* plan, int kind,
+                                                 void* stream_) {
+  return x3_iter_fwd(q, img_x, bsq, B, N, D, opart, rpart, y, rsum, unorm, plan, nullptr, nullptr, nullptr, kind,
+                     stream_);
 }
 
 // Backward of one iteration on the bf16 x 3 path: same contract as pn_meanshift_iter_bwd_f32 with
@@ -1907,16 +1958,15 @@ extern "C" int pn_meanshift_x3_iter_bwd_f32(const float* gy, const float* y, con
 }
 
 // The same with the plan the forward call of this iteration used (NULL = dense).
-extern "C" int pn_meanshift_x3_iter_bwd_plan_f32(const float* gy, const float* y, const float* q,
-                                                 const float* x, const void* img_x, const float* rsum,
-                                                 const float* unorm, const float* bsq, int B, int N, int D,
-                                                 float* gu, float* cs, void* img_q, void* img_gu,
-                                                 float* opart_q, float* opart_x, float* gq, float* gx,
-                                                 const void* plan, void* stream_) {
+static int x3_iter_bwd(const float* gy, const float* y, const float* q, const float* x, const void* img_x,
+                       const float* rsum, const float* unorm, const float* bsq, int B, int N, int D, float* gu,
+                       float* cs, void* img_q, void* img_gu, float* opart_q, float* opart_x, float* gq, float* gx,
+                       const void* plan, int kind, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  X3_CHECK_KIND(kind, plan, "pn_meanshift_x3_iter_bwd");
   PN_CHECK_ARG(gy && y && q && x && img_x && rsum && unorm && bsq && gu && cs && img_q && img_gu &&
                    opart_q && opart_x && gq && gx,
-               "pn_meanshift_x3_iter_bwd_f32: null pointer");
+               "pn_meanshift_x3_iter_bwd: null pointer");
   PN_CHECK_ARG(D == MS_D, "pn_meanshift: embedding size %d unsupported (built for %d)", D, MS_D);
   const int ntiles = (int)pn_align_up(N, 64) / 32;
   const X3Plan pv = x3_plan_view(plan, B, N, ntiles);
@@ -1964,7 +2014,7 @@ extern "C" int pn_meanshift_x3_iter_bwd_plan_f32(const float* gy, const float* y
   {
     PN_PROF("meanshift_bwd_rows", stream);
     dim3 grid(S, pn_cdiv(N, 32 * X3_WAVES(1)), B);
-    X3_LAUNCH_PP(1, grid, dim3(64 * X3_WAVES(1)), stream, q, (const float*)gu,
+    X3_LAUNCH_KIND(1, kind, grid, dim3(64 * X3_WAVES(1)), stream, q, (const float*)gu,
                        (const u32x4*)img_x, nullptr, (const float*)cs, (const float*)alpha, bsq, N,
                        ntiles, tps, opart_q, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0);
   }
@@ -1972,7 +2022,7 @@ extern "C" int pn_meanshift_x3_iter_bwd_plan_f32(const float* gy, const float* y
   {
     PN_PROF("meanshift_bwd_cols", stream);
     dim3 grid2(S2, pn_cdiv(N, 32 * X3_WAVES(2)), B);
-    X3_LAUNCH_PP(2, grid2, dim3(64 * X3_WAVES(2)), stream, x, nullptr,
+    X3_LAUNCH_KIND(2, kind, grid2, dim3(64 * X3_WAVES(2)), stream, x, nullptr,
                        (const u32x4*)img_q, (const u32x4*)img_gu, (const float*)cs,
                        (const float*)alpha, bsq, N, ntiles, tps2, opart_x, nullptr, nullptr, nullptr, nullptr,
                        nullptr, 0, 0, 0, 0, 0, 0);
@@ -1982,4 +2032,25 @@ extern "C" int pn_meanshift_x3_iter_bwd_plan_f32(const float* gy, const float* y
                      opart_q, opart_x, ND4, S, S2, gq, gx);
   PN_CHECK_LAUNCH();
   return PN_OK;
+}
+
+extern "C" int pn_meanshift_x3_iter_bwd_plan_f32(const float* gy, const float* y, const float* q,
+                                                 const float* x, const void* img_x, const float* rsum,
+                                                 const float* unorm, const float* bsq, int B, int N, int D,
+                                                 float* gu, float* cs, void* img_q, void* img_gu,
+                                                 float* opart_q, float* opart_x, float* gq, float* gx,
+                                                 const void* plan, void* stream_) {
+  return x3_iter_bwd(gy, y, q, x, img_x, rsum, unorm, bsq, B, N, D, gu, cs, img_q, img_gu, opart_q, opart_x, gq, gx,
+                     plan, X3_GAUSS, stream_);
+}
+
+// ... with the kernel profile of the forward call (kind != 0: dense only, a plan is refused)
+extern "C" int pn_meanshift_x3_iter_bwd_kind_f32(const float* gy, const float* y, const float* q,
+                                                 const float* x, const void* img_x, const float* rsum,
+                                                 const float* unorm, const float* bsq, int B, int N, int D,
+                                                 float* gu, float* cs, void* img_q, void* img_gu,
+                                                 float* opart_q, float* opart_x, float* gq, float* gx,
+                                                 const void* plan, int kind, void* stream_) {
+  return x3_iter_bwd(gy, y, q, x, img_x, rsum, unorm, bsq, B, N, D, gu, cs, img_q, img_gu, opart_q, opart_x, gq, gx,
+                     plan, kind, stream_);
 }

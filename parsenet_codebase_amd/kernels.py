@@ -570,11 +570,18 @@ def meanshift_x3_plan_visited(plans, B, N):
     return torch.stack([p[:n].sum(dtype=torch.float32) for p in plans]).mean() / float(n)
 
 
-def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=False):
+KERNEL_GAUSSIAN, KERNEL_EPANECHNIKOV = 0, 1      # PN_MS_KERNEL_* of include/parsenet_hip.h
+
+
+def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=False, kind=KERNEL_GAUSSIAN):
     """``out`` = (y (B,N,D), rsum (B,N), unorm (B,N)) contiguous fp32 tensors to write into (slices of
     the buffers that keep all iterates of a call together), or None: allocated here.  ``want_info``: also
-    return meanshift_x3_tileinfo(y) — the caps come out of the launch that combines the partial results."""
+    return meanshift_x3_tileinfo(y) — the caps come out of the launch that combines the partial results.
+    ``kind``: the kernel profile; the Epanechnikov kernel launches dense (the library refuses it a plan) and
+    returns no caps."""
     B, N, D = q.shape
+    if kind != KERNEL_GAUSSIAN and want_info:
+        raise ValueError("meanshift_x3_iter_fwd: the caps of the iterate feed the plans, which are Gaussian-only")
     if out is not None:
         y, rsum, unorm = out
         for t, shp in ((y, (B, N, D)), (rsum, (B, N)), (unorm, (B, N))):
@@ -584,24 +591,29 @@ def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=Fa
         y = torch.empty_like(q)
         rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
         unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
-    info = None
-    if want_info:
-        T = (N + 63) // 64 * 2
-        info = (torch.empty((B, T, 2, D), dtype=torch.float32, device=q.device),
-                torch.empty((B, T, 2), dtype=torch.float32, device=q.device),
-                torch.empty((B, T, 2), dtype=torch.float32, device=q.device))
+    if not want_info:
+        with _lib.on_device(q.device):
+            rc = _lib.load().pn_meanshift_x3_iter_fwd_kind_f32(ptr(q), ptr(x_image), ptr(bsq), B, N, D, ptr(ws.opart),
+                                                               ptr(ws.rpart), ptr(y), ptr(rsum), ptr(unorm),
+                                                               ptr(plan), int(kind), current_stream(q.device))
+        check(rc, "pn_meanshift_x3_iter_fwd_kind_f32")
+        return y, rsum, unorm
+    T = (N + 63) // 64 * 2
+    info = (torch.empty((B, T, 2, D), dtype=torch.float32, device=q.device),
+            torch.empty((B, T, 2), dtype=torch.float32, device=q.device),
+            torch.empty((B, T, 2), dtype=torch.float32, device=q.device))
     with _lib.on_device(q.device):
         rc = _lib.load().pn_meanshift_x3_iter_fwd_info_f32(ptr(q), ptr(x_image), ptr(bsq), B, N, D, ptr(ws.opart),
                                                            ptr(ws.rpart), ptr(y), ptr(rsum), ptr(unorm),
-                                                           ptr(plan), ptr(info[0]) if info else None,
-                                                           ptr(info[1]) if info else None,
-                                                           ptr(info[2]) if info else None, current_stream(q.device))
+                                                           ptr(plan), ptr(info[0]), ptr(info[1]), ptr(info[2]),
+                                                           current_stream(q.device))
     check(rc, "pn_meanshift_x3_iter_fwd_info_f32")
-    return (y, rsum, unorm, info) if want_info else (y, rsum, unorm)
+    return y, rsum, unorm, info
 
 
-def meanshift_x3_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx, plan=None):
-    """bf16 x 3 counterpart of meanshift_iter_bwd: returns dL/dq, adds into ``gx``."""
+def meanshift_x3_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx, plan=None, kind=KERNEL_GAUSSIAN):
+    """bf16 x 3 counterpart of meanshift_iter_bwd: returns dL/dq, adds into ``gx``.  ``kind``: the kernel
+    profile of the forward call."""
     B, N, D = x.shape
     gy = _f32c(gy, "gy")
     gq = torch.empty_like(x)
@@ -611,11 +623,11 @@ def meanshift_x3_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx, plan=N
         ws.x3_imgs = [torch.empty(nbytes, dtype=torch.uint8, device=x.device) for _ in range(2)]
     im = ws.x3_imgs
     with _lib.on_device(x.device):
-        rc = lib.pn_meanshift_x3_iter_bwd_plan_f32(ptr(gy), ptr(y), ptr(q), ptr(x), ptr(x_image), ptr(rsum),
+        rc = lib.pn_meanshift_x3_iter_bwd_kind_f32(ptr(gy), ptr(y), ptr(q), ptr(x), ptr(x_image), ptr(rsum),
                                                    ptr(unorm), ptr(bsq), B, N, D, ptr(ws.gu), ptr(ws.cs),
                                                    ptr(im[0]), ptr(im[1]), ptr(ws.opart), ptr(ws.opart_x), ptr(gq),
-                                                   ptr(gx), ptr(plan), current_stream(x.device))
-    check(rc, "pn_meanshift_x3_iter_bwd_plan_f32")
+                                                   ptr(gx), ptr(plan), int(kind), current_stream(x.device))
+    check(rc, "pn_meanshift_x3_iter_bwd_kind_f32")
     return gq
 
 
@@ -658,11 +670,12 @@ def _msw_bsq(bsq, B, device):
     return bsq.contiguous()
 
 
-def meanshift_w_iter_fwd(q, x, bsq, ws, out=None):
+def meanshift_w_iter_fwd(q, x, bsq, ws, out=None, kind=KERNEL_GAUSSIAN):
     """One mean-shift iteration at width 32 or 64: q (B,N,D) the current iterate, x (B,N,D) the data, bsq
     (B) squared bandwidths -> (y (B,N,D), rsum (B,N), unorm (B,N)), the triple meanshift_x3_iter_fwd
     returns.  ``out``: contiguous fp32 tensors of those shapes to write into.  The tile images of ``x`` in the
-    workspace are reused when they were built from this very ``x`` (see MeanShiftWWorkspace), rebuilt otherwise."""
+    workspace are reused when they were built from this very ``x`` (see MeanShiftWWorkspace), rebuilt otherwise.
+    ``kind``: the kernel profile (KERNEL_GAUSSIAN / KERNEL_EPANECHNIKOV)."""
     require_cuda(q, x, bsq)
     q, x = _f32c(q, "q"), _f32c(x, "x")
     B, N, D = x.shape
@@ -679,16 +692,18 @@ def meanshift_w_iter_fwd(q, x, bsq, ws, out=None):
         rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
         unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
     with _lib.on_device(q.device):
-        rc = _lib.load().pn_meanshift_w_iter_fwd_f32(ptr(q), ptr(x), ptr(bsq), B, N, D, ptr(y), ptr(rsum), ptr(unorm),
-                                                     ptr(ws.buf), ws.buf.numel(), int(ws.holds_image_of(x)),
-                                                     current_stream(q.device))
-    check(rc, "pn_meanshift_w_iter_fwd_f32")
+        rc = _lib.load().pn_meanshift_w_iter_fwd_kind_f32(ptr(q), ptr(x), ptr(bsq), B, N, D, ptr(y), ptr(rsum),
+                                                          ptr(unorm), ptr(ws.buf), ws.buf.numel(),
+                                                          int(ws.holds_image_of(x)), int(kind),
+                                                          current_stream(q.device))
+    check(rc, "pn_meanshift_w_iter_fwd_kind_f32")
     ws.took_image_of(x)
     return y, rsum, unorm
 
 
-def meanshift_w_iter_bwd(gy, y, q, x, rsum, unorm, bsq, ws, gx):
-    """Backward of that iteration (recomputes the kernel values): returns dL/dq, adds into ``gx``."""
+def meanshift_w_iter_bwd(gy, y, q, x, rsum, unorm, bsq, ws, gx, kind=KERNEL_GAUSSIAN):
+    """Backward of that iteration (recomputes the kernel values): returns dL/dq, adds into ``gx``.  ``kind``:
+    the kernel profile of the forward call."""
     require_cuda(gy, y, q, x, rsum, unorm, bsq, gx)
     x = _f32c(x, "x")
     B, N, D = x.shape
@@ -703,10 +718,11 @@ def meanshift_w_iter_bwd(gy, y, q, x, rsum, unorm, bsq, ws, gx):
         raise TypeError("meanshift_w_iter_bwd: gx must be contiguous fp32")
     gq = torch.empty_like(x)
     with _lib.on_device(x.device):
-        rc = _lib.load().pn_meanshift_w_iter_bwd_f32(ptr(gy), ptr(y), ptr(q), ptr(x), ptr(rsum), ptr(unorm), ptr(bsq),
-                                                     B, N, D, ptr(gq), ptr(gx), ptr(ws.buf), ws.buf.numel(),
-                                                     int(ws.holds_image_of(x)), current_stream(x.device))
-    check(rc, "pn_meanshift_w_iter_bwd_f32")
+        rc = _lib.load().pn_meanshift_w_iter_bwd_kind_f32(ptr(gy), ptr(y), ptr(q), ptr(x), ptr(rsum), ptr(unorm),
+                                                          ptr(bsq), B, N, D, ptr(gq), ptr(gx), ptr(ws.buf),
+                                                          ws.buf.numel(), int(ws.holds_image_of(x)), int(kind),
+                                                          current_stream(x.device))
+    check(rc, "pn_meanshift_w_iter_bwd_kind_f32")
     ws.took_image_of(x)
     return gq
 

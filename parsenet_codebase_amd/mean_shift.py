@@ -66,7 +66,7 @@ LAST_PLAN_STATS = None      # diagnostics of the most recent call (only filled w
 # The iterations hold points and final iterate in the locality order the exact pruning needs.
 WANT_NEAREST = False
 LAST_NEAREST = None
-# Embedding widths other than 128 (gaussian kernel).  Widths 32 and 64 have kernels of their own
+# Embedding widths other than 128.  Widths 32 and 64 have kernels of their own
 # (csrc/meanshift_w.hip: bf16 x 3 arithmetic, dense launches, recompute backward); every other width
 # D <= 128 is zero-padded to the next of 32 / 64 / 128 — zero columns are exact in every product and
 # stay zero through the renormalisation — and sliced on the way out.  The block-sparse plans, the
@@ -76,10 +76,20 @@ LAST_NEAREST = None
 # with PARSENET_MS_ARITH = f32 / fp16x2 narrow widths are padded to 128 as well, so the arithmetic asked
 # for is the arithmetic that runs.  Like the 128-wide path, all of this takes float32 tensors on the GPU
 # only (the tensor expressions these widths ran before accepted any device and dtype; those remain for
-# widths above 128 and the Epanechnikov kernel).
+# widths above 128).
+# The Epanechnikov kernel (kernel_type other than "gaussian", src/mean_shift.py:64-68) runs on the same
+# kernels at the same widths with the same padding: a second, compile-time form of the elementwise stage
+# between the two GEMMs (K = max(0, 3/4 (1 - dist / b^2)); derivative 3/2 / b^2 on the support, 0 off it).
+# Its launches are always dense and in the given order — the plans' bounds are those of the exponential —
+# so it neither reads nor moves SPARSE's bookkeeping (_AUTO, CALLS, CALLS_W, LAST_NEAREST); CALLS_EPA
+# counts its calls.  It exists in bf16 x 3 arithmetic only: ``MeanShift.mean_shift_`` sends an Epanechnikov
+# call to it for float32 GPU tensors of width <= 128 under PARSENET_MS_ARITH = bf16x3 and keeps the tensor
+# expressions (N x N per iteration, any device and dtype) for everything else, so the arithmetic asked for
+# is the arithmetic that runs.  mean_shift_iterations_state / centre_rows / shift_async are Gaussian-only.
 NARROW = os.environ.get("PARSENET_MS_NARROW", "native")
 NARROW_WIDTHS = (32, 64)
 CALLS_W = 0                 # calls of the iterations that ran on the width-32 / width-64 kernels
+CALLS_EPA = 0               # calls of the iterations that ran the fused Epanechnikov kernel (any width)
 
 
 def kernel_width(D):
@@ -301,16 +311,54 @@ def _run_iterations_w(x, bsq, iterations, stacked):
             "iterates_all": it_all, "rsums_all": rs_all, "norms_all": nr_all}
 
 
+def _run_iterations_epa(X, bsq, iterations):
+    """``_run_iterations`` with the Epanechnikov kernel: dense launches in the given order at width 32, 64 or
+    128 (bf16 x 3), the same dict (no plans, no permutation)."""
+    global CALLS_EPA
+    x = X.contiguous()
+    B, N, D = x.shape
+    if ARITH != "bf16x3":
+        raise ValueError("the fused Epanechnikov kernel is bf16x3 only, PARSENET_MS_ARITH is %r "
+                         "(MeanShift.mean_shift_ runs the tensor expressions then)" % ARITH)
+    if D != 128 and kernel_width(D) != D:
+        raise ValueError("_run_iterations_epa: width %d does not run as it is; mean_shift_iterations zero-pads it "
+                         "to %s" % (D, kernel_width(D)))
+    CALLS_EPA += 1
+    narrow = D != 128
+    x3 = ws = None
+    if iterations > 0:
+        x3 = None if narrow else K.meanshift_x3_split(x)
+        ws = K.MeanShiftWWorkspace(B, N, D, x.device) if narrow else K.MeanShiftWorkspace(B, N, D, x.device)
+    iterates, rsums, norms = [x], [], []
+    q = x
+    for it in range(iterations):
+        if narrow:
+            q, r, n = K.meanshift_w_iter_fwd(q, x, bsq, ws, kind=K.KERNEL_EPANECHNIKOV)
+        else:
+            q, r, n = K.meanshift_x3_iter_fwd(q, x3, bsq, ws, None, kind=K.KERNEL_EPANECHNIKOV)
+        iterates.append(q)
+        rsums.append(r)
+        norms.append(n)
+    return {"x": x, "xt": x3, "x3": x3, "kern": "w" if narrow else _SPLIT["bf16x3"], "sparse": False, "perm": None,
+            "inv": None, "q": q, "iterates": iterates, "rsums": rsums, "norms": norms, "plans": [],
+            "iterates_all": None, "rsums_all": None, "norms_all": None}
+
+
 class _MeanShiftIterations(torch.autograd.Function):
     """X (B,N,D) unit rows, bsq (B) squared bandwidths -> iterate after ``iterations`` steps.
-    Saves only the iterates, row sums and norms (O(T N D)); the backward recomputes the kernel."""
+    Saves only the iterates, row sums and norms (O(T N D)); the backward recomputes the kernel.
+    ``kind``: the kernel profile (kernels.KERNEL_GAUSSIAN / KERNEL_EPANECHNIKOV) of forward and backward."""
 
     @staticmethod
-    def forward(ctx, X, bsq, iterations):
+    def forward(ctx, X, bsq, iterations, kind=K.KERNEL_GAUSSIAN):
         D = X.shape[2]
-        st = _run_iterations(X, bsq, iterations, rel_eps=PLAN_REL_EPS_DENSE_BWD)   # (its backward reuses the plans)
+        if kind != K.KERNEL_GAUSSIAN:
+            st = _run_iterations_epa(X, bsq, iterations)
+        else:
+            st = _run_iterations(X, bsq, iterations, rel_eps=PLAN_REL_EPS_DENSE_BWD)   # (its backward reuses the plans)
         sparse, q = st["sparse"], st["q"]
         ctx.iterations = iterations
+        ctx.kind = kind
         ctx.x3 = st["x3"]
         ctx.kern = st["kern"]
         ctx.sparse = sparse
@@ -337,15 +385,19 @@ class _MeanShiftIterations(torch.autograd.Function):
         if ctx.narrow:
             ws = K.MeanShiftWWorkspace(B, N, D, x.device, backward=True) if T > 0 else None
             for it in reversed(range(T)):
-                g = K.meanshift_w_iter_bwd(g, iterates[it + 1], iterates[it], x, rsums[it], norms[it], bsq, ws, gX)
+                g = K.meanshift_w_iter_bwd(g, iterates[it + 1], iterates[it], x, rsums[it], norms[it], bsq, ws, gX,
+                                           kind=ctx.kind)
             gX += g  # the first iterate is X itself
-            return gX, None, None
+            return gX, None, None, None
         ws = K.MeanShiftWorkspace(B, N, D, x.device, backward=True, exact_f32=ctx.x3 is None)
         if ctx.sparse:
             perm, inv = saved[-2], saved[-1]
             g = torch.gather(g, 1, perm.unsqueeze(2).expand(-1, -1, D))
         for it in reversed(range(T)):
-            if ctx.sparse:
+            if ctx.kind != K.KERNEL_GAUSSIAN:
+                g = K.meanshift_x3_iter_bwd(g, iterates[it + 1], iterates[it], x, ctx.x3, rsums[it], norms[it], bsq,
+                                            ws, gX, None, kind=ctx.kind)
+            elif ctx.sparse:
                 g = K.meanshift_x3_iter_bwd(g, iterates[it + 1], iterates[it], x, ctx.x3, rsums[it], norms[it], bsq,
                                             ws, gX, plans[it])
             elif ctx.x3 is not None:
@@ -356,13 +408,15 @@ class _MeanShiftIterations(torch.autograd.Function):
         gX += g  # the first iterate is X itself
         if ctx.sparse:
             gX = torch.gather(gX, 1, inv.unsqueeze(2).expand(-1, -1, D))
-        return gX, None, None
+        return gX, None, None, None
 
 
-def mean_shift_iterations(X, b, iterations):
+def mean_shift_iterations(X, b, iterations, kernel_type="gaussian"):
     """X (N,D) or (B,N,D), D <= 128; b scalar / 0-dim tensor / (B,) tensor of bandwidths.  Widths without
-    kernels of their own run zero-padded to the next width that has them (``kernel_width``)."""
+    kernels of their own run zero-padded to the next width that has them (``kernel_width``).  ``kernel_type``:
+    "gaussian", or anything else for the Epanechnikov kernel as in the reference (bf16x3 arithmetic only)."""
     require_cuda(X)
+    kind = K.KERNEL_GAUSSIAN if kernel_type == "gaussian" else K.KERNEL_EPANECHNIKOV
     squeeze = X.dim() == 2
     Xb = X.unsqueeze(0) if squeeze else X
     B, D = Xb.shape[0], Xb.shape[2]
@@ -375,7 +429,7 @@ def mean_shift_iterations(X, b, iterations):
     if bt.numel() == 1:
         bt = bt.expand(B)
     bsq = (bt.detach() ** 2).contiguous()
-    out = _MeanShiftIterations.apply(Xb, bsq, int(iterations))
+    out = _MeanShiftIterations.apply(Xb, bsq, int(iterations), kind)
     if W != D:
         out = out[..., :D]
     return out[0] if squeeze else out
@@ -518,10 +572,15 @@ class MeanShift:
 
     # -- src/mean_shift.py:45-79 ---------------------------------------------------------
     def mean_shift_(self, X, b, iterations=10, kernel_type="gaussian"):
-        if kernel_type == "gaussian" and kernel_width(X.shape[-1]) is not None:
-            return mean_shift_iterations(X, b, iterations), X
-        # Epanechnikov kernel / embeddings wider than 128: never used by the training path; plain
-        # tensor expressions on the GPU (materialises N x N like the reference)
+        if kernel_width(X.shape[-1]) is not None:
+            if kernel_type == "gaussian":
+                return mean_shift_iterations(X, b, iterations), X
+            # any other kernel_type is the Epanechnikov kernel (src/mean_shift.py:64-68): fused where its
+            # kernels exist — bf16 x 3 arithmetic, float32 on the GPU
+            if ARITH == "bf16x3" and X.is_cuda and X.dtype == torch.float32:
+                return mean_shift_iterations(X, b, iterations, kernel_type=kernel_type), X
+        # embeddings wider than 128, and the Epanechnikov kernel on other arithmetics, devices or dtypes:
+        # never used by the training path; plain tensor expressions (materialises N x N like the reference)
         new_X = X.clone()
         for _ in range(iterations):
             Kmat = self.kernel_between(new_X, X, kernel_type, b)

@@ -1,0 +1,118 @@
+"""CPU: the entry points that carry the kernel profile (Gaussian / Epanechnikov) of the fused mean-shift
+kernels are declared in include/parsenet_hip.h, exported by the built library and bound in the ctypes table;
+the library refuses an Epanechnikov launch with a block-sparse plan before it launches anything; and
+MeanShift.mean_shift_ keeps the tensor expressions for Epanechnikov calls the fused kernels do not serve."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "parsenet_hip.h")
+NAMES = ("pn_meanshift_w_iter_fwd_kind_f32", "pn_meanshift_w_iter_bwd_kind_f32",
+         "pn_meanshift_x3_iter_fwd_kind_f32", "pn_meanshift_x3_iter_bwd_kind_f32")
+PN_ERR_ARG, PN_ERR_UNSUPPORTED = -1, -4
+
+
+@pytest.fixture(scope="module")
+def lib_path():
+    from parsenet_codebase_amd import build
+    return build.build(verbose=False)
+
+
+def test_header_declares_the_kind_entry_points():
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = set(re.findall(r"\b(pn_[a-z0-9_]+)\s*\(", txt))
+    assert not [n for n in NAMES if n not in declared]
+    assert re.search(r"#define\s+PN_MS_KERNEL_GAUSSIAN\s+0\b", txt)
+    assert re.search(r"#define\s+PN_MS_KERNEL_EPANECHNIKOV\s+1\b", txt)
+
+
+def test_library_exports_and_ctypes_table_binds_them(lib_path):
+    from parsenet_codebase_amd import _lib, kernels
+    lib = ctypes.CDLL(lib_path)
+    assert not [n for n in NAMES if not hasattr(lib, n)]
+    assert not [n for n in NAMES if n not in _lib.SIGNATURES]
+    # one int more than the entry point without the kind, in front of the stream
+    for name in NAMES:
+        res, args = _lib.SIGNATURES[name]
+        res0, args0 = _lib.SIGNATURES[name.replace("_kind_", "_plan_" if "_x3_" in name else "_")]
+        assert res == res0 and args == args0[:-1] + [ctypes.c_int] + args0[-1:]
+    assert (kernels.KERNEL_GAUSSIAN, kernels.KERNEL_EPANECHNIKOV) == (0, 1)
+
+
+def _dummies(n):
+    """n distinct non-null addresses of host memory the calls below never get to touch."""
+    keep = [ctypes.create_string_buffer(64) for _ in range(n)]
+    return keep, [ctypes.addressof(k) for k in keep]
+
+
+@pytest.mark.parametrize("kind,plan,want", [(1, True, PN_ERR_UNSUPPORTED), (2, False, PN_ERR_ARG), (-1, True, PN_ERR_ARG)])
+def test_planned_epanechnikov_launch_is_refused(lib_path, kind, plan, want):
+    """Block-sparse plans bound the tail of the exponential: an Epanechnikov call with a plan is an error, not a
+    Gaussian answer and not a dense launch behind the caller's back.  The check precedes every launch, so it
+    runs (and returns) on a machine without a GPU."""
+    from parsenet_codebase_amd import _lib
+    lib = _lib.load()
+    keep, p = _dummies(17)
+    pl = p[16] if plan else None
+    rc = lib.pn_meanshift_x3_iter_fwd_kind_f32(p[0], p[1], p[2], 1, 4096, 128, p[3], p[4], p[5], p[6], p[7], pl, kind,
+                                               None)
+    assert rc == want
+    msg = lib.pn_last_error().decode()
+    assert ("plan" in msg) if want == PN_ERR_UNSUPPORTED else ("kind" in msg)
+    rc = lib.pn_meanshift_x3_iter_bwd_kind_f32(*p[:8], 1, 4096, 128, *p[8:16], pl, kind, None)
+    assert rc == want
+    assert ("plan" in lib.pn_last_error().decode()) if want == PN_ERR_UNSUPPORTED else True
+
+
+def test_width_kernels_refuse_an_unknown_kind(lib_path):
+    from parsenet_codebase_amd import _lib
+    lib = _lib.load()
+    keep, p = _dummies(11)
+    big = 1 << 40
+    assert lib.pn_meanshift_w_iter_fwd_kind_f32(p[0], p[1], p[2], 1, 300, 64, p[3], p[4], p[5], p[6], big, 0, 2,
+                                                None) == PN_ERR_ARG
+    assert "kind" in lib.pn_last_error().decode()
+    assert lib.pn_meanshift_w_iter_bwd_kind_f32(*p[:7], 1, 300, 64, p[7], p[8], p[9], big, 0, 7, None) == PN_ERR_ARG
+    assert "kind" in lib.pn_last_error().decode()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("d", [50, 128])
+def test_epanechnikov_on_the_cpu_still_runs_the_tensor_expressions(d, dtype):
+    """What worked before still works: a CPU tensor (any dtype) with the Epanechnikov kernel gets the reference's
+    tensor expressions — the oracle's result bit for bit — and is not counted as a fused call."""
+    import torch
+    from oracle import ref_torch as R
+    from parsenet_codebase_amd import mean_shift as MSM
+    g = torch.Generator().manual_seed(d)
+    X = torch.nn.functional.normalize(torch.randn(160, d, generator=g, dtype=getattr(torch, dtype)), dim=1)
+    b = torch.tensor(1.1, dtype=X.dtype)
+    before = MSM.CALLS_EPA
+    xg = X.clone().requires_grad_(True)
+    yg, same = MSM.MeanShift().mean_shift_(xg, b, 3, kernel_type="epa")
+    xr = X.clone().requires_grad_(True)
+    yr, _ = R.MeanShift().mean_shift_(xr, b, 3, kernel_type="epa")
+    assert same is xg and yg.dtype == X.dtype and MSM.CALLS_EPA == before
+    assert torch.equal(yg, yr)
+    w = torch.randn(160, d, generator=g, dtype=X.dtype)
+    (yg * w).sum().backward()
+    (yr * w).sum().backward()
+    assert torch.equal(xg.grad, xr.grad)
+
+
+def test_fused_epanechnikov_refuses_what_it_has_no_kernel_for(monkeypatch):
+    """mean_shift_iterations is the fused path and nothing else: CPU tensors, other arithmetics and widths
+    above 128 are errors there (MeanShift.mean_shift_ decides; it never gets this far with them)."""
+    import torch
+    from parsenet_codebase_amd import mean_shift as MSM
+    monkeypatch.setattr(MSM, "ARITH", "bf16x3")
+    with pytest.raises(RuntimeError):
+        MSM.mean_shift_iterations(torch.zeros(40, 64), 0.5, 1, kernel_type="epa")
+    with pytest.raises(ValueError):
+        MSM._run_iterations_epa(torch.zeros(1, 40, 50), torch.ones(1), 1)
+    monkeypatch.setattr(MSM, "ARITH", "f32")
+    with pytest.raises(ValueError, match="bf16x3"):
+        MSM._run_iterations_epa(torch.zeros(1, 40, 128), torch.ones(1), 1)
