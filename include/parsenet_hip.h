@@ -267,7 +267,7 @@ int pn_gemm_x3_wgrad_f32(const float* gy, const float* x, int B, int M, int K, i
  * (B,R,D) are the R rows of the incoming gradient, of the step's result and of its input iterate, rsum,
  * unorm (B,R) the saved row sums and pre-normalisation norms of those rows, x (B,N,D) the data, bsq (B)
  * the squared bandwidths.  Writes gq (B,R,D), the gradient w.r.t. the input rows, and ADDS the step's
- * gradient w.r.t. the data into gx (B,N,D).  D = 128.  No atomics.  workspace:
+ * gradient w.r.t. the data into gx (B,N,D).  D in {32, 64, 128}.  No atomics.  workspace:
  * pn_meanshift_rows_bwd_workspace(B, N) bytes. */
 size_t pn_meanshift_rows_bwd_workspace(int B, int N);
 int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum, const float* unorm,
@@ -595,7 +595,7 @@ int pn_edgeconv_bwd_stats_f32(const float* gout, const float* yext, const float*
                               void* stream);
 
 /* Triplet embedding loss, src/segment_loss.py:85-123 (EmbeddingLoss.triplet_loss, the arithmetic
- * after the numpy sampling): E (rows,D) unit-row embedding (D = 128); item p of P has num <= 32
+ * after the numpy sampling): E (rows,D) unit-row embedding (D in {32, 64, 128}); item p of P has num <= 32
  * anchor/positive rows ia[p][:] and negative rows ib[p][:] (row indices into E) and a weight w[p]
  * (1 / (pairs of its shape + 1e-8));  c_ij = relu(|a_i - p_j|^2 - |a_i - n_j|^2 + margin),
  * item_loss[p] = w[p] * (sum_ij c_ij - sum_i c_ii) / (#(c_ij > 0) + 1), loss[0] = sum_p item_loss[p];
@@ -615,7 +615,7 @@ int pn_triplet_bwd_f32(const float* E, int rows, int D, const int64_t* ia, const
 /* Memberships of the fitting stage in one pass: src/residual_utils.py:120 (weights = center @
  * embedding^T), src/fitting_utils.py:306-325 (weights_normalize) and the labels of
  * src/mean_shift.py:176-178 (arg-max over the centres, first index on ties).
- * cen (B,CP,D) centre rows padded to CP in {16,32,64} (rows >= ncl[b] ignored), emb (B,N,D), D = 128,
+ * cen (B,CP,D) centre rows padded to CP in {16,32,64} (rows >= ncl[b] ignored), emb (B,N,D), D in {32, 64, 128},
  * bw (B), ncl (B) int64.  Outputs Wraw, prob, Wn (B,CP,N) (padding rows of prob / Wn are zero),
  * rowstat (B,CP,4) = (min_n prob, max_n (prob - min) + eps, arg-min, arg-max as int bits), labels
  * (B,N) int64 or NULL.  _bwd: gWraw (B,CP,N) from gWn, the exact gradient of weights_normalize

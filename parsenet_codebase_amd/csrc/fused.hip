@@ -330,13 +330,18 @@ extern "C" int pn_triplet_fwd_f32(const float* E, int rows, int D, const int64_t
   PN_CHECK_ARG(E && ia && ib && w && item_loss && item_scale && loss, "pn_triplet_fwd_f32: null pointer");
   PN_CHECK_ARG(P > 0 && rows > 0 && num >= 1 && num <= TRI_MAXNUM, "pn_triplet_fwd_f32: P=%d num=%d (max %d)", P,
                num, TRI_MAXNUM);
-  if (D != 128) {
-    pn_set_error("pn_triplet_fwd_f32: embedding size %d (128 supported)", D);
+  if (D != 32 && D != 64 && D != 128) {
+    pn_set_error("pn_triplet_fwd_f32: embedding size %d (supported: {32, 64, 128})", D);
     return PN_ERR_UNSUPPORTED;
   }
   PN_PROF("triplet_fwd", stream);
-  hipLaunchKernelGGL(pn_triplet_fwd_kernel<128>, dim3(P), dim3(256), 0, stream, E, ia, ib, w, num, margin, item_loss,
-                     item_scale);
+#define TRI_F(W)                                                                                                  \
+  hipLaunchKernelGGL(pn_triplet_fwd_kernel<W>, dim3(P), dim3(256), 0, stream, E, ia, ib, w, num, margin, item_loss, \
+                     item_scale)
+  if (D == 32) TRI_F(32);
+  else if (D == 64) TRI_F(64);
+  else TRI_F(128);
+#undef TRI_F
   hipLaunchKernelGGL(pn_triplet_sum_kernel, dim3(1), dim3(64), 0, stream, (const float*)item_loss, P, loss);
   PN_CHECK_LAUNCH();
   return PN_OK;
@@ -352,17 +357,24 @@ extern "C" int pn_triplet_bwd_f32(const float* E, int rows, int D, const int64_t
   hipStream_t stream = (hipStream_t)stream_;
   PN_CHECK_ARG(E && ia && ib && item_scale && gout && gE && workspace, "pn_triplet_bwd_f32: null pointer");
   PN_CHECK_ARG(P > 0 && rows > 0 && num >= 1 && num <= TRI_MAXNUM, "pn_triplet_bwd_f32: P=%d num=%d", P, num);
-  if (D != 128) {
-    pn_set_error("pn_triplet_bwd_f32: embedding size %d (128 supported)", D);
+  if (D != 32 && D != 64 && D != 128) {
+    pn_set_error("pn_triplet_bwd_f32: embedding size %d (supported: {32, 64, 128})", D);
     return PN_ERR_UNSUPPORTED;
   }
   PN_CHECK_ARG(workspace_bytes >= pn_triplet_bwd_workspace(P, num, D), "pn_triplet_bwd_f32: workspace too small");
   float* slots = (float*)workspace;
   PN_PROF("triplet_bwd", stream);
-  hipLaunchKernelGGL(pn_triplet_bwd_kernel<128>, dim3(P), dim3(256), 0, stream, E, ia, ib, item_scale, gout, num,
-                     margin, slots);
-  hipLaunchKernelGGL(pn_triplet_combine_kernel<128>, dim3(P * 2 * num), dim3(128), 0, stream, (const float*)slots, ia,
-                     ib, num, P * 2 * num, gE);
+  // (the combine kernel runs D threads per slot — half a wave at D = 32: it reduces nothing across lanes, its only
+  // cross-thread steps are workgroup barriers and LDS bit masks, which hold at any workgroup size)
+#define TRI_B(W)                                                                                                     \
+  hipLaunchKernelGGL(pn_triplet_bwd_kernel<W>, dim3(P), dim3(256), 0, stream, E, ia, ib, item_scale, gout, num,      \
+                     margin, slots);                                                                                 \
+  hipLaunchKernelGGL(pn_triplet_combine_kernel<W>, dim3(P * 2 * num), dim3(W), 0, stream, (const float*)slots, ia,   \
+                     ib, num, P * 2 * num, gE)
+  if (D == 32) { TRI_B(32); }
+  else if (D == 64) { TRI_B(64); }
+  else { TRI_B(128); }
+#undef TRI_B
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -377,9 +389,9 @@ extern "C" int pn_triplet_bwd_f32(const float* E, int rows, int D, const int64_t
 //   label   = first arg-max over c < ncl of Wraw[c]      (src/mean_shift.py:176-178)
 // then per row c (second kernel): m = min_n prob, s = max_n (prob - m) + eps and
 //   Wn[c][n] = ncl > 1 ? (prob - m) / s : prob           (:319-324)
-// Block = 64 points x 4 waves; wave w owns centre rows [w * CP/4, (w+1) * CP/4).
-#define MB_D 128
-template <int CP>
+// Block = 64 points x 4 waves; wave w owns centre rows [w * CP/4, (w+1) * CP/4).  MB_D: the embedding width, 32, 64
+// or 128 (the backward kernels never see it: they work on (B,CP,N) arrays).
+template <int CP, int MB_D>
 __global__ __launch_bounds__(256) void pn_member_fwd_kernel(const float* __restrict__ cen, const float* __restrict__ emb,
                                                             const float* __restrict__ bw, const int64_t* __restrict__ ncl,
                                                             int N, float* __restrict__ Wraw, float* __restrict__ prob,
@@ -602,18 +614,23 @@ extern "C" int pn_membership_fwd_f32(const float* cen, const float* emb, const f
   hipStream_t stream = (hipStream_t)stream_;
   PN_CHECK_ARG(cen && emb && bw && ncl && Wraw && prob && Wn && rowstat, "pn_membership_fwd_f32: null pointer");
   PN_CHECK_ARG(B > 0 && N > 0, "pn_membership_fwd_f32: B=%d N=%d", B, N);
-  if (D != MB_D || (CP != 16 && CP != 32 && CP != 64)) {
-    pn_set_error("pn_membership_fwd_f32: D=%d CP=%d (D = 128 and CP in {16, 32, 64} supported)", D, CP);
+  if ((D != 32 && D != 64 && D != 128) || (CP != 16 && CP != 32 && CP != 64)) {
+    pn_set_error("pn_membership_fwd_f32: D=%d CP=%d (supported: D in {32, 64, 128} and CP in {16, 32, 64})", D, CP);
     return PN_ERR_UNSUPPORTED;
   }
   PN_PROF("membership_fwd", stream);
   dim3 grid(pn_cdiv(N, 64), B);
-#define MB_F(C)                                                                                              \
-  hipLaunchKernelGGL(pn_member_fwd_kernel<C>, grid, dim3(256), 0, stream, cen, emb, bw, ncl, N, Wraw, prob, \
+#define MB_F(C, W)                                                                                              \
+  hipLaunchKernelGGL((pn_member_fwd_kernel<C, W>), grid, dim3(256), 0, stream, cen, emb, bw, ncl, N, Wraw, prob, \
                      labels)
-  if (CP == 16) MB_F(16);
-  else if (CP == 32) MB_F(32);
-  else MB_F(64);
+#define MB_FW(W)          \
+  if (CP == 16) MB_F(16, W); \
+  else if (CP == 32) MB_F(32, W); \
+  else MB_F(64, W)
+  if (D == 32) { MB_FW(32); }
+  else if (D == 64) { MB_FW(64); }
+  else { MB_FW(128); }
+#undef MB_FW
 #undef MB_F
   hipLaunchKernelGGL(pn_member_rows_kernel, dim3(B * CP), dim3(256), 0, stream, (const float*)prob, ncl, CP, N, eps,
                      Wn, (float4*)rowstat);

@@ -29,22 +29,52 @@
 // 50 000 cycles of arithmetic per workgroup) took 101 us: with 150 KiB of staged operands there is one
 // 4-wave workgroup per CU and nothing hides its load -> barrier -> product -> barrier -> read-add-write chain;
 // the matrix-core version was removed again.
+//
+// Widths.  The four kernels are templates on the embedding width MR_D (32, 64, 128) and the row stride MR_LD of the
+// staged operands; the entry points dispatch on D.  MR_LD = MR_D + 4 floats at every width: rows stay 16-byte
+// aligned, and the sixteen rows a 16-lane group of a ds_read_b128 touches start at 16-byte slots
+// (row * MR_LD) mod 64 = 4 row (132, 68) or 36 row mod 64 (36) — sixteen distinct multiples of 4 below 64 in all
+// three cases, i.e. all 64 banks once: conflict-free.  The 64 x 64 blocks (gs, K / r, gs transposed: 51 KiB) do not
+// shrink with the width, the three staged operands do:
+//   width 128: 150.8 KiB of LDS per workgroup -> 1 workgroup per CU (160 KiB)
+//   width  64: 102.8 KiB                      -> 1 workgroup per CU
+//   width  32:  78.8 KiB                      -> 2 workgroups per CU
+// Each thread owns 4 features of 64 * (MR_D / 4) / 256 = 8 / 4 / 2 rows in the two accumulation phases; every sum
+// runs over the same index in the same order at every width, and the <128> instantiation is the round-4 kernel
+// operation for operation.  The workspace is sized for width 128 whatever D is (its entry point has no D).
 #include "common.h"
 #include <cstdlib>
 
-#define MR_D 128
+#define MR_DMAX 128     // widest instantiation: sizes the workspace
 #define MR_R 64        // rows per batch item (zero padded)
 #define MR_CB 64       // data points per workgroup
-#define MR_LD 132      // row stride of the staged operands (floats): 16-byte aligned, 4 banks apart
+#define MR_LDOF(D) ((D) + 4)      // row stride of the staged operands (floats), see "Widths" above
 #define MR_LG 68       // row stride of the 64 x 64 blocks
 #define MR_LOG2E 1.4426950408889634f
 #define MR_LIM2 (75.0f * MR_LOG2E)
 
 __device__ static inline float4 mr_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// NV (8, 4 or 2) consecutive floats of an LDS row
+template <int NV>
+__device__ static inline void mr_ldn(const float* p, float* v) {
+  if constexpr (NV == 8) {
+    const float4 a = mr_ld4(p), b = mr_ld4(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else if constexpr (NV == 4) {
+    const float4 a = mr_ld4(p);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+    const float2 a = *reinterpret_cast<const float2*>(p);
+    v[0] = a.x; v[1] = a.y;
+  }
+}
 
 // gu, c, alpha and 1 / r of the R rows, one wave per row (as pn_ms_prep_bwd_kernel): once per step, not once
 // per workgroup of the main kernel (there the sixteen rows of a wave were sixteen dependent round trips to
-// memory: 60 % of the launch)
+// memory: 60 % of the launch).  Lane l holds features l and (width 128) l + 64; at width 32 the upper half wave
+// holds zeros.
+template <int MR_D, int MR_LD>
 __global__ __launch_bounds__(256) void pn_ms_rows_prep_kernel(const float* __restrict__ gy, const float* __restrict__ y,
                                                               const float* __restrict__ rsum, const float* __restrict__ unorm,
                                                               const float* __restrict__ bsq, int R, float* __restrict__ gu,
@@ -56,8 +86,12 @@ __global__ __launch_bounds__(256) void pn_ms_rows_prep_kernel(const float* __res
   float u0 = 0.f, u1 = 0.f, c = 0.f, al = 0.f, ri = 0.f;
   if (r < R) {
     const size_t base = ((size_t)b * R + r) * MR_D;
-    const float y0 = y[base + lane], y1 = y[base + lane + 64];
-    const float g0 = gy[base + lane], g1 = gy[base + lane + 64];
+    const bool lo = MR_D >= 64 || lane < MR_D;          // (width 32: the upper half wave holds zeros)
+    float y0 = 0.f, y1 = 0.f, g0 = 0.f, g1 = 0.f;
+    if (lo) y0 = y[base + lane];
+    if constexpr (MR_D == 128) y1 = y[base + lane + 64];
+    if (lo) g0 = gy[base + lane];
+    if constexpr (MR_D == 128) g1 = gy[base + lane + 64];
     const float nn = unorm[(size_t)b * R + r], rr = rsum[(size_t)b * R + r];
     const float yg = pn_wave_sum(y0 * g0 + y1 * g1);
     u0 = (g0 - y0 * yg) / nn;
@@ -67,8 +101,8 @@ __global__ __launch_bounds__(256) void pn_ms_rows_prep_kernel(const float* __res
     ri = 1.0f / rr;
   }
   float* g = gu + ((size_t)b * MR_R + r) * MR_D;
-  g[lane] = u0;
-  g[lane + 64] = u1;
+  if (lane < MR_D) g[lane] = u0;
+  if constexpr (MR_D == 128) g[lane + 64] = u1;
   if (lane == 0) {
     float* sp = scal + ((size_t)b * MR_R + r) * 4;
     sp[0] = c;
@@ -78,6 +112,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_prep_kernel(const float* __res
   }
 }
 
+template <int MR_D, int MR_LD>
 __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
     const float* __restrict__ gu, const float* __restrict__ scal, const float* __restrict__ q,
     const float* __restrict__ x, const float* __restrict__ bsq, int N, int R, int nblk, float* __restrict__ gx,
@@ -93,6 +128,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
   float* sa = sc + MR_R;                    // alpha_i
   float* sr = sa + MR_R;                    // 1 / r_i
   const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+  constexpr int MR_L4 = MR_D == 128 ? 5 : MR_D == 64 ? 4 : 3;      // log2 of the float4s per row
 
   const int j0 = blk * MR_CB;
   const float bs = bsq[b];
@@ -101,7 +137,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
 
   // ---- stage: x rows (zero past N), q rows, gu rows + the per-row scalars
   for (int it = tid; it < MR_CB * (MR_D / 4); it += 256) {
-    const int r = it >> 5, c4 = it & 31;
+    const int r = it >> MR_L4, c4 = it & (MR_D / 4 - 1);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (j0 + r < N) v = mr_ld4(xb + (size_t)(j0 + r) * MR_D + 4 * c4);
     *reinterpret_cast<float4*>(Xs + r * MR_LD + 4 * c4) = v;
@@ -110,7 +146,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
     *reinterpret_cast<float4*>(Qs + r * MR_LD + 4 * c4) = w;
   }
   for (int it = tid; it < MR_R * (MR_D / 4); it += 256) {      // gu rows and the per-row scalars (pn_ms_rows_prep_kernel)
-    const int r = it >> 5, c4 = it & 31;
+    const int r = it >> MR_L4, c4 = it & (MR_D / 4 - 1);
     *reinterpret_cast<float4*>(Us + r * MR_LD + 4 * c4) = mr_ld4(gu + ((size_t)b * MR_R + r) * MR_D + 4 * c4);
   }
   if (tid < MR_R) {
@@ -176,21 +212,22 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
   }
   __syncthreads();
 
-  const int f4 = tid & 31, grp = tid >> 5;    // 4 features, 8 rows or columns per thread
-  // ---- gX rows j = 8 grp .. 8 grp + 7: sum_i gs_ij q_i + (K_ij / r_i) gu_i
+  constexpr int NF4 = MR_D / 4;               // threads across a row (4 features each)
+  constexpr int RPT = MR_CB * NF4 / 256;      // rows or columns per thread: 8, 4, 2 at width 128, 64, 32
+  const int f4 = tid & (NF4 - 1), grp = tid >> MR_L4;
+  // ---- gX rows j = RPT grp .. RPT grp + RPT - 1: sum_i gs_ij q_i + (K_ij / r_i) gu_i
   {
-    float4 acc[8];
+    float4 acc[RPT];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = 0; e < RPT; ++e) acc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = 0; i < MR_R; ++i) {
       const float4 qv = mr_ld4(Qs + i * MR_LD + 4 * f4);
       const float4 uv = mr_ld4(Us + i * MR_LD + 4 * f4);
-      const float4 g0 = mr_ld4(GS + i * MR_LG + 8 * grp), g1 = mr_ld4(GS + i * MR_LG + 8 * grp + 4);
-      const float4 k0 = mr_ld4(KR + i * MR_LG + 8 * grp), k1 = mr_ld4(KR + i * MR_LG + 8 * grp + 4);
-      const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      const float kv[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+      float gv[RPT], kv[RPT];
+      mr_ldn<RPT>(GS + i * MR_LG + RPT * grp, gv);
+      mr_ldn<RPT>(KR + i * MR_LG + RPT * grp, kv);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
+      for (int e = 0; e < RPT; ++e) {
         acc[e].x = __builtin_fmaf(gv[e], qv.x, acc[e].x);
         acc[e].y = __builtin_fmaf(gv[e], qv.y, acc[e].y);
         acc[e].z = __builtin_fmaf(gv[e], qv.z, acc[e].z);
@@ -202,8 +239,8 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
       }
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int j = j0 + 8 * grp + e;
+    for (int e = 0; e < RPT; ++e) {
+      const int j = j0 + RPT * grp + e;
       if (j < N) {
         float4* o = reinterpret_cast<float4*>(gx + ((size_t)b * N + j) * MR_D + 4 * f4);
         float4 v = *o;
@@ -215,17 +252,17 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
       }
     }
   }
-  // ---- partial of gq rows i = 8 grp .. 8 grp + 7 over this block's columns
+  // ---- partial of gq rows i = RPT grp .. RPT grp + RPT - 1 over this block's columns
   {
-    float4 acc[8];
+    float4 acc[RPT];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = 0; e < RPT; ++e) acc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = 0; j < MR_CB; ++j) {
       const float4 xv = mr_ld4(Xs + j * MR_LD + 4 * f4);
-      const float4 g0 = mr_ld4(GT + j * MR_LG + 8 * grp), g1 = mr_ld4(GT + j * MR_LG + 8 * grp + 4);
-      const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+      float gv[RPT];
+      mr_ldn<RPT>(GT + j * MR_LG + RPT * grp, gv);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
+      for (int e = 0; e < RPT; ++e) {
         acc[e].x = __builtin_fmaf(gv[e], xv.x, acc[e].x);
         acc[e].y = __builtin_fmaf(gv[e], xv.y, acc[e].y);
         acc[e].z = __builtin_fmaf(gv[e], xv.z, acc[e].z);
@@ -234,11 +271,12 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
     }
     float* pb = gq_part + ((size_t)b * nblk + blk) * MR_R * MR_D;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) *reinterpret_cast<float4*>(pb + (8 * grp + e) * MR_D + 4 * f4) = acc[e];
+    for (int e = 0; e < RPT; ++e) *reinterpret_cast<float4*>(pb + (RPT * grp + e) * MR_D + 4 * f4) = acc[e];
   }
 }
 
 // gq (B,R,D) = sum over the column blocks, in block order; one float4 per thread
+template <int MR_D, int MR_LD>
 __global__ __launch_bounds__(256) void pn_ms_rows_reduce_kernel(const float* __restrict__ gq_part, int R, int nblk,
                                                                 float* __restrict__ gq) {
   const int b = blockIdx.y;
@@ -272,7 +310,8 @@ __global__ __launch_bounds__(256) void pn_ms_rows_reduce_kernel(const float* __r
 }
 
 // gx[b, rows[b, r], :] += g[b, r, :] for r = 0 .. R-1 IN ORDER (rows may repeat among the padded
-// entries): one workgroup per batch item, 32 threads per row of 128 floats
+// entries): one workgroup per batch item, 32 threads per row, of which the first MR_D / 4 hold a float4 each
+template <int MR_D, int MR_LD>
 __global__ __launch_bounds__(256) void pn_ms_rows_scatter_kernel(const float* __restrict__ g, const int64_t* __restrict__ rows,
                                                                  int N, int R, float* __restrict__ gx) {
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -282,7 +321,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_scatter_kernel(const float* __
   for (int r0 = 0; r0 < R; r0 += 8) {
     for (int turn = 0; turn < 8; ++turn) {
       const int r = r0 + turn;
-      if (sub == turn && r < R) {
+      if (sub == turn && r < R && f4 < MR_D / 4) {
         const int64_t row = rows[(size_t)b * R + r];
         if (row >= 0 && row < N) {
           float4* o = reinterpret_cast<float4*>(gx + ((size_t)b * N + row) * MR_D + 4 * f4);
@@ -300,31 +339,25 @@ __global__ __launch_bounds__(256) void pn_ms_rows_scatter_kernel(const float* __
   }
 }
 
-static size_t mr_part_bytes(int B, int N) { return pn_align_up((size_t)B * pn_cdiv(N, MR_CB) * MR_R * MR_D * sizeof(float), 256); }
-static size_t mr_gu_bytes(int B) { return pn_align_up((size_t)B * MR_R * MR_D * sizeof(float), 256); }
+// (sized for the widest instantiation: pn_meanshift_rows_bwd_workspace has no D)
+static size_t mr_part_bytes(int B, int N) {
+  return pn_align_up((size_t)B * pn_cdiv(N, MR_CB) * MR_R * MR_DMAX * sizeof(float), 256);
+}
+static size_t mr_gu_bytes(int B) { return pn_align_up((size_t)B * MR_R * MR_DMAX * sizeof(float), 256); }
 extern "C" size_t pn_meanshift_rows_bwd_workspace(int B, int N) {
   return mr_part_bytes(B, N) + mr_gu_bytes(B) + pn_align_up((size_t)B * MR_R * 4 * sizeof(float), 256);
 }
 
-// One step of the row-restricted backward.  gy, y, q (B,R,D), rsum, unorm (B,R): the R rows of the
-// incoming gradient, of the step's result, of its input iterate and of its saved row sums / norms;
-// x (B,N,D) the data; bsq (B).  Writes gq (B,R,D) and ADDS the step's contribution into gx (B,N,D).
-extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum,
-                                         const float* unorm, const float* x, const float* bsq, int B, int N, int D,
-                                         int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
-                                         hipStream_t stream) {
-  PN_CHECK_ARG(D == MR_D, "pn_meanshift_rows_bwd_f32: D must be %d, got %d", MR_D, D);
-  PN_CHECK_ARG(R >= 1 && R <= MR_R, "pn_meanshift_rows_bwd_f32: 1 <= R <= %d, got %d", MR_R, R);
-  PN_CHECK_ARG(B >= 1 && N >= 1, "pn_meanshift_rows_bwd_f32: empty input");
+template <int MR_D>
+static int mr_rows_bwd(const float* gy, const float* y, const float* q, const float* rsum, const float* unorm,
+                       const float* x, const float* bsq, int B, int N, int R, float* gq, float* gx, void* workspace,
+                       hipStream_t stream) {
+  constexpr int MR_LD = MR_LDOF(MR_D);
   const int nblk = pn_cdiv(N, MR_CB);
-  if (workspace_bytes < pn_meanshift_rows_bwd_workspace(B, N)) {
-    pn_set_error("pn_meanshift_rows_bwd_f32: workspace too small");
-    return PN_ERR_WORKSPACE;
-  }
   const size_t lds_valu = (size_t)(3 * MR_R * MR_LD + 3 * MR_R * MR_LG + 3 * MR_R) * sizeof(float);
-  static unsigned attr_devs = 0;
+  static unsigned attr_devs = 0;       // (one per instantiation)
   if (pn_first_on_device(&attr_devs)) {
-    PN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pn_ms_rows_bwd_kernel),
+    PN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pn_ms_rows_bwd_kernel<MR_D, MR_LD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_valu));
   }
   float* part = static_cast<float*>(workspace);
@@ -332,22 +365,48 @@ extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const 
   float* scal = reinterpret_cast<float*>(static_cast<char*>(workspace) + mr_part_bytes(B, N) + mr_gu_bytes(B));
   {
     PN_PROF("meanshift_rows_bwd", stream);
-    hipLaunchKernelGGL(pn_ms_rows_prep_kernel, dim3(MR_R / 4, B), dim3(256), 0, stream, gy, y, rsum, unorm, bsq, R, gu, scal);
-    hipLaunchKernelGGL(pn_ms_rows_bwd_kernel, dim3(nblk, B), dim3(256), lds_valu, stream, (const float*)gu,
+    hipLaunchKernelGGL((pn_ms_rows_prep_kernel<MR_D, MR_LD>), dim3(MR_R / 4, B), dim3(256), 0, stream, gy, y, rsum, unorm,
+                       bsq, R, gu, scal);
+    hipLaunchKernelGGL((pn_ms_rows_bwd_kernel<MR_D, MR_LD>), dim3(nblk, B), dim3(256), lds_valu, stream, (const float*)gu,
                        (const float*)scal, q, x, bsq, N, R, nblk, gx, part);
   }
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pn_ms_rows_reduce_kernel, dim3(pn_cdiv(R * (MR_D / 4), 256), B), dim3(256), 0, stream, part, R, nblk,
-                     gq);
+  hipLaunchKernelGGL((pn_ms_rows_reduce_kernel<MR_D, MR_LD>), dim3(pn_cdiv(R * (MR_D / 4), 256), B), dim3(256), 0, stream,
+                     (const float*)part, R, nblk, gq);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
 
+// One step of the row-restricted backward.  gy, y, q (B,R,D), rsum, unorm (B,R): the R rows of the
+// incoming gradient, of the step's result, of its input iterate and of its saved row sums / norms;
+// x (B,N,D) the data; bsq (B); D = 32, 64 or 128.  Writes gq (B,R,D) and ADDS the step's contribution into gx (B,N,D).
+extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum,
+                                         const float* unorm, const float* x, const float* bsq, int B, int N, int D,
+                                         int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
+                                         hipStream_t stream) {
+  PN_CHECK_ARG(D == 32 || D == 64 || D == 128, "pn_meanshift_rows_bwd_f32: D must be one of {32, 64, 128}, got %d", D);
+  PN_CHECK_ARG(R >= 1 && R <= MR_R, "pn_meanshift_rows_bwd_f32: 1 <= R <= %d, got %d", MR_R, R);
+  PN_CHECK_ARG(B >= 1 && N >= 1, "pn_meanshift_rows_bwd_f32: empty input");
+  if (workspace_bytes < pn_meanshift_rows_bwd_workspace(B, N)) {
+    pn_set_error("pn_meanshift_rows_bwd_f32: workspace too small");
+    return PN_ERR_WORKSPACE;
+  }
+  if (D == 32) return mr_rows_bwd<32>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
+  if (D == 64) return mr_rows_bwd<64>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
+  return mr_rows_bwd<128>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
+}
+
 extern "C" int pn_meanshift_rows_scatter_add_f32(const float* g, const int64_t* rows, int B, int N, int D, int R,
                                                  float* gx, hipStream_t stream) {
-  PN_CHECK_ARG(D == MR_D, "pn_meanshift_rows_scatter_add_f32: D must be %d, got %d", MR_D, D);
+  PN_CHECK_ARG(D == 32 || D == 64 || D == 128, "pn_meanshift_rows_scatter_add_f32: D must be one of {32, 64, 128}, got %d",
+               D);
   PN_CHECK_ARG(B >= 1 && R >= 1, "pn_meanshift_rows_scatter_add_f32: empty input");
-  hipLaunchKernelGGL(pn_ms_rows_scatter_kernel, dim3(B), dim3(256), 0, stream, g, rows, N, R, gx);
+  if (D == 32)
+    hipLaunchKernelGGL((pn_ms_rows_scatter_kernel<32, MR_LDOF(32)>), dim3(B), dim3(256), 0, stream, g, rows, N, R, gx);
+  else if (D == 64)
+    hipLaunchKernelGGL((pn_ms_rows_scatter_kernel<64, MR_LDOF(64)>), dim3(B), dim3(256), 0, stream, g, rows, N, R, gx);
+  else
+    hipLaunchKernelGGL((pn_ms_rows_scatter_kernel<128, MR_LDOF(128)>), dim3(B), dim3(256), 0, stream, g, rows, N, R, gx);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

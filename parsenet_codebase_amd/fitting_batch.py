@@ -47,6 +47,13 @@ CMAX = 64          # padded list of cluster centres (the guard retries above 49 
 ROWS_BWD = os.environ.get("PARSENET_MS_ROWS_BWD", "1") != "0"
 # the open and the closed SplineNet of a fitting stage on two streams (0: one after the other)
 SPLINE_STREAMS = os.environ.get("PARSENET_SPLINE_STREAMS", "1") != "0"
+# Which path a call took (like MSM.CALLS_W): shapes whose clustering and memberships came out of the batched
+# stage / went alone through the per-shape API (ev.guard_mean_shift: embeddings wider than 128, tie-flagged
+# selection rows, the guard's retry above 49 clusters, a shape outside the selection kernel's fast path) ...
+CALLS_STAGE = {"batched": 0, "per_shape": 0}
+# ... and calls of memberships() by the form that ran: csrc/fused.hip's kernels or the tensor expressions
+CALLS_MEMBERSHIP = {"fused": 0, "tensor": 0}
+MEMBERSHIP_WIDTHS = (32, 64, 128)      # embedding widths pn_membership_fwd_f32 is instantiated for
 _SIDE = {}
 
 
@@ -84,7 +91,7 @@ def _fitter_bases(fitter, dev):
 
 
 def bandwidth_batch(X, quantile, num_samples=10000):
-    """MeanShift.compute_bandwidth (src/mean_shift.py:115-137) for every shape of X (B,N,128):
+    """MeanShift.compute_bandwidth (src/mean_shift.py:115-137) for every shape of X (B,N,D), D <= 128:
     (bw (B,) clamped at 0.003, flagged rows per shape (B,)) or None outside the selection
     kernel's fast path.  Needs num_samples >= N (every row is used, the shuffle is immaterial;
     the caller still draws it from numpy's RNG)."""
@@ -111,7 +118,7 @@ def bandwidth_batch(X, quantile, num_samples=10000):
 
 
 def nms_batch(new_X, X, bw, width=None, labels=True, nearest=None):
-    """MeanShift.nms (src/mean_shift.py:139-179) for all shapes at once.  new_X, X (B,N,128)
+    """MeanShift.nms (src/mean_shift.py:139-179) for all shapes at once.  new_X, X (B,N,D)
     detached, bw (B,).  Returns a dict: labels (B,N) int64 (None with ``labels=False``: the caller
     takes them from the membership kernel it runs anyway), cid (B,CMAX) int64 ascending centre ids
     (padded), ncl, nocc, nflag (B,) and the padded ``width`` of the neighbour matrix.  None outside
@@ -165,7 +172,7 @@ def centre_labels(new_X, X, cid, ncl, bw):
     """labels = first arg-max over the pruned centres of centre . x (src/mean_shift.py:176-178)."""
     B, N, D = X.shape
     Csel = torch.gather(new_X, 1, cid.unsqueeze(2).expand(-1, -1, D))
-    if D == 128 and cid.shape[1] in (16, 32, 64):
+    if D in MEMBERSHIP_WIDTHS and cid.shape[1] in (16, 32, 64):
         return K.membership_fwd(Csel, X, bw, torch.clamp(ncl, max=cid.shape[1]), EPS, want_labels=True)[4]
     cvalid = torch.arange(cid.shape[1], device=X.device).unsqueeze(0) < ncl.unsqueeze(1)
     sc = torch.bmm(Csel, X.transpose(1, 2))                                     # (B,CMAX,N)
@@ -202,7 +209,7 @@ def weights_normalize_batch(Wraw, bw, ncl):
 
 
 class _Membership(torch.autograd.Function):
-    """centres (B,CP,128) padded, embedding (B,N,128), bandwidths (B,), cluster counts (B,) ->
+    """centres (B,CP,D) padded, embedding (B,N,D), D = 32, 64 or 128, bandwidths (B,), cluster counts (B,) ->
     (Wn, Wraw) (B,CP,N): src/residual_utils.py:120 + fitting_utils.weights_normalize in two
     launches (csrc/fused.hip); backward: two launches + the two GEMMs onto centres and embedding."""
 
@@ -222,13 +229,19 @@ class _Membership(torch.autograd.Function):
 
 
 def memberships(cen, emb, bw, ncl):
-    """(Wn, Wraw) for padded centre rows; the fused kernels for 128-d embeddings and at most 64
-    centres (the guard retries above 49 anyway), tensor expressions otherwise."""
+    """(Wn, Wraw) for padded centre rows; the fused kernels for embeddings of width <= 128 (32, 64 and 128 as
+    they are, the others zero-padded to the next of them: a zero column adds nothing to a dot product) and at most
+    64 centres (the guard retries above 49 anyway), tensor expressions otherwise."""
     B, Cp, D = cen.shape
-    if D == 128 and Cp <= 64:
+    W = next((w for w in MEMBERSHIP_WIDTHS if D <= w), None)
+    if W is not None and Cp <= 64:
+        CALLS_MEMBERSHIP["fused"] += 1
         CP = 16 if Cp <= 16 else 32 if Cp <= 32 else 64
-        cen = torch.nn.functional.pad(cen, (0, 0, 0, CP - Cp))
+        cen = torch.nn.functional.pad(cen, (0, W - D, 0, CP - Cp))
+        if W != D:
+            emb = torch.nn.functional.pad(emb, (0, W - D))
         return _Membership.apply(cen, emb, bw.contiguous(), ncl)[:2]
+    CALLS_MEMBERSHIP["tensor"] += 1
     Wraw = torch.bmm(cen, emb.transpose(1, 2))
     return weights_normalize_batch(Wraw, bw, ncl), Wraw
 
@@ -547,10 +560,17 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
     fitter = ev.fitter
 
     # ---- clustering, all shapes ---------------------------------------------------------
+    # The batched path at every width the mean-shift kernels serve (MSM.kernel_width: 32, 64, 128; with
+    # PARSENET_MS_NARROW=pad128 always 128): a narrower embedding is zero-padded ONCE, here — the pad is
+    # differentiable, zero columns are exact in every product and survive the renormalisation — and bandwidth,
+    # iterations, NMS, centre rows, memberships and labels all run at width W.  Narrow widths have no plans:
+    # LAST_NEAREST is then None and nms_batch takes its dot_select branch.
+    W = MSM.kernel_width(D)
+    embw = emb if W is None or W == D else torch.nn.functional.pad(emb, (0, W - D))
     state = None
     with torch.no_grad(), record_function("fit:bandwidth"):
-        bwres = bandwidth_batch(emb, quantile)
-    if bwres is not None and D == 128:
+        bwres = bandwidth_batch(embw, quantile) if W is not None else None
+    if bwres is not None:
         bw, bwflag = bwres
         with record_function("fit:meanshift_fwd"):
             # (a planned call also returns every point's nearest shifted point, the first step of the NMS:
@@ -561,9 +581,9 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
                 # MSM.centre_rows below — and the backward then runs those rows alone; PARSENET_MS_ROWS_BWD=0:
                 # the dense backward passes over all rows, same gradient up to the summation order)
                 if ROWS_BWD:
-                    new_X, ms_state = MSM.mean_shift_iterations_state(emb, bw, iterations)
+                    new_X, ms_state = MSM.mean_shift_iterations_state(embw, bw, iterations)
                 else:
-                    new_X, ms_state = MSM.mean_shift_iterations(emb, bw, iterations), None
+                    new_X, ms_state = MSM.mean_shift_iterations(embw, bw, iterations), None
             finally:
                 MSM.WANT_NEAREST = False
             nearest, MSM.LAST_NEAREST = MSM.LAST_NEAREST, None
@@ -573,15 +593,15 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
             downloaded — the memberships of ALL CMAX padded centre rows (rows >= ncl are masked in
             the kernel), whose first output are the cluster labels the host is waiting for."""
             with torch.no_grad(), record_function("fit:nms"):
-                st = nms_batch(new_X.detach(), emb.detach(), bw, width, labels=False, nearest=nearest)
+                st = nms_batch(new_X.detach(), embw.detach(), bw, width, labels=False, nearest=nearest)
             if st is not None:
                 with record_function("fit:memberships"):
                     if ms_state is not None:
-                        cen_all = MSM.centre_rows(emb, ms_state, st["cid"])                            # (B,CMAX,D)
+                        cen_all = MSM.centre_rows(embw, ms_state, st["cid"])                           # (B,CMAX,W)
                     else:
-                        cen_all = torch.gather(new_X, 1, st["cid"].unsqueeze(2).expand(-1, -1, D))
+                        cen_all = torch.gather(new_X, 1, st["cid"].unsqueeze(2).expand(-1, -1, W))
                     st["cen"] = cen_all
-                    st["Wn"], st["Wraw"], st["labels"] = _Membership.apply(cen_all, emb, bw, torch.clamp(st["ncl"], max=CMAX))
+                    st["Wn"], st["Wraw"], st["labels"] = _Membership.apply(cen_all, embw, bw, torch.clamp(st["ncl"], max=CMAX))
             return st
         state = cluster(nms_width_guess(ev, B, N))
     with torch.no_grad():
@@ -661,13 +681,15 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
         if fast and not predrawn:
             np.random.shuffle(np.arange(N))
         if fast and ncl_h[b] <= 49:
-            centers.append(state["cen"][b, :int(ncl_h[b])])
+            CALLS_STAGE["batched"] += 1
+            centers.append(state["cen"][b, :int(ncl_h[b]), :D])       # (the padding columns are zeros)
             bws.append(bw[b])
             cluster_ids.append(lab_h[b].astype(np.int64))
         else:
             # tie-flagged selection rows or the guard's retry above 49 clusters: this shape alone on
             # the synchronous path
             all_fast = False
+            CALLS_STAGE["per_shape"] += 1
             q = quantile * 1.2 if (fast and ncl_h[b] > 49) else quantile
             c, bwb, ids = ev.guard_mean_shift(emb[b], q, iterations, kernel_type="gaussian")
             centers.append(c)

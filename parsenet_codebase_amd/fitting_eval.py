@@ -47,6 +47,9 @@ _REFIT = {"open": dict(size_u=20, size_v=20, up=(1600, 2000), sub=1600, degree=2
 # ---------------------------------------------------------------------------------------------
 # clustering of all shapes (no gradient)
 # ---------------------------------------------------------------------------------------------
+CALLS_CLUSTER = {"batched": 0, "per_shape": 0}      # shapes by the branch of cluster_shapes that clustered them
+
+
 def cluster_shapes(ev, emb, quantile, iterations):
     """guard_mean_shift of every shape (src/residual_utils.py:69-84) -> (clusters, calls): clusters[b] =
     (centres (C,128), bandwidth (0-dim tensor), cluster ids (N,) int64 numpy), calls[b] = the number of
@@ -62,16 +65,20 @@ def cluster_shapes(ev, emb, quantile, iterations):
     dev = emb.device
     fast = None
     with torch.no_grad():
-        bwres = bandwidth_batch(emb, quantile) if D == 128 else None
+        # every width up to 128 takes the batched branch at the width its kernels run at (fitting_batch._fitting_stage:
+        # zero-padded once; zero columns are exact in every product); the centres are sliced back to D below
+        W = MSM.kernel_width(D)
+        embw = emb if W is None or W == D else torch.nn.functional.pad(emb, (0, W - D))
+        bwres = bandwidth_batch(embw, quantile) if W is not None else None
         if bwres is not None:
             bw, bwflag = bwres
             MSM.WANT_NEAREST = True
             try:
-                new_X, _ = MSM.mean_shift_iterations_state(emb, bw, iterations)
+                new_X, _ = MSM.mean_shift_iterations_state(embw, bw, iterations)
             finally:
                 MSM.WANT_NEAREST = False
             nearest, MSM.LAST_NEAREST = MSM.LAST_NEAREST, None
-            st = nms_batch(new_X, emb, bw, None, labels=True, nearest=nearest)
+            st = nms_batch(new_X, embw, bw, None, labels=True, nearest=nearest)
             if st is not None:
                 pack = torch.cat([st["labels"].reshape(-1), st["cid"].reshape(-1), st["ncl"], bwflag,
                                   st["nflag"]]).to(torch.int32).cpu().numpy()              # download 1
@@ -84,10 +91,12 @@ def cluster_shapes(ev, emb, quantile, iterations):
         if ok and fast[4][b] <= 49:
             new_X, bw, lab_h, cid_h, ncl_h = fast[:5]
             cid = h2d(cid_h[b, :int(ncl_h[b])].astype(np.int64), dev)
-            clusters.append((new_X[b][cid], bw[b], lab_h[b].astype(np.int64)))
+            clusters.append((new_X[b][cid][:, :D], bw[b], lab_h[b].astype(np.int64)))
             calls.append(1)
+            CALLS_CLUSTER["batched"] += 1
             continue
         # the guard's loop on the per-shape API; a fast attempt that found more than 49 clusters was its first call
+        CALLS_CLUSTER["per_shape"] += 1
         q, n = (quantile * 1.2, 1) if ok else (quantile, 0)
         while True:
             _, center, bandwidth, ids = ev.ms.mean_shift(emb[b], 10000, q, iterations, kernel_type="gaussian")

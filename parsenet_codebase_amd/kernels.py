@@ -849,8 +849,8 @@ def gemm_x3_wgrad(gy, x, want_bias=False):
 
 def meanshift_rows_bwd(gy, y, q, rsum, unorm, x, bsq, gx, ws=None):
     """One step of the mean-shift backward restricted to R <= 64 rows per batch item (csrc/meanshift_rows.hip;
-    src/mean_shift.py:45-79 maps every row on its own): gy, y, q (B,R,128), rsum, unorm (B,R), x (B,N,128),
-    bsq (B).  Returns gq (B,R,128); ADDS the step's gradient w.r.t. the data into gx (B,N,128)."""
+    src/mean_shift.py:45-79 maps every row on its own): gy, y, q (B,R,D), rsum, unorm (B,R), x (B,N,D),
+    bsq (B); D = 32, 64 or 128.  Returns gq (B,R,D); ADDS the step's gradient w.r.t. the data into gx (B,N,D)."""
     require_cuda(gy, y, q, rsum, unorm, x, bsq, gx)
     gy, y, q, x = _f32c(gy, "gy"), _f32c(y, "y"), _f32c(q, "q"), _f32c(x, "x")
     rsum, unorm, bsq = _f32c(rsum, "rsum"), _f32c(unorm, "unorm"), _f32c(bsq, "bsq")
@@ -1204,7 +1204,7 @@ def edgeconv_bwd_stats(gout, yext, mean, rstd, gamma, beta, groups, per_sample, 
 
 
 def triplet_fwd(E, ia, ib, w, margin):
-    """E (rows,128) fp32; ia, ib (P,num) int64 row indices; w (P,) fp32 -> (loss (1,), item_scale (P,))."""
+    """E (rows,D) fp32, D = 32, 64 or 128; ia, ib (P,num) int64 row indices; w (P,) fp32 -> (loss (1,), item_scale (P,))."""
     require_cuda(E, ia, ib, w)
     E = _f32c(E, "E")
     ia, ib = _i64c(ia, "ia"), _i64c(ib, "ib")
@@ -1222,7 +1222,7 @@ def triplet_fwd(E, ia, ib, w, margin):
 
 
 def triplet_bwd(E, ia, ib, item_scale, gout, margin):
-    """d loss / d E (rows,128) scaled by gout (1,)."""
+    """d loss / d E (rows,D) scaled by gout (1,)."""
     require_cuda(E, gout)
     P, num = ia.shape
     gE = torch.zeros_like(E)
@@ -1238,7 +1238,7 @@ def triplet_bwd(E, ia, ib, item_scale, gout, margin):
 
 
 def membership_fwd(cen, emb, bw, ncl, eps, want_labels=False):
-    """cen (B,CP,128), emb (B,N,128), bw (B,), ncl (B,) int64 -> Wraw, prob, Wn (B,CP,N), rowstat (B,CP,4),
+    """cen (B,CP,D), emb (B,N,D), D = 32, 64 or 128, bw (B,), ncl (B,) int64 -> Wraw, prob, Wn (B,CP,N), rowstat (B,CP,4),
     labels (B,N) int64 or None."""
     require_cuda(cen, emb, bw, ncl)
     cen, emb, bw = _f32c(cen, "cen"), _f32c(emb, "emb"), _f32c(bw, "bw")

@@ -43,11 +43,21 @@ def normalized_rows(x):
 
 
 FUSED = True        # False: the tensor-expression form of the same arithmetic (tests compare the two)
+TRIPLET_WIDTHS = (32, 64, 128)     # embedding widths csrc/fused.hip's triplet kernels are instantiated for
+CALLS_TRIPLET_FUSED = 0            # groups of sampled segment pairs that ran the fused triplet kernels
+
+
+def triplet_width(D):
+    """The width a D-wide embedding runs the fused triplet kernels at (zero-padded up to it), None above 128."""
+    for W in TRIPLET_WIDTHS:
+        if D <= W:
+            return W
+    return None
 
 
 class _TripletItems(torch.autograd.Function):
     """The arithmetic of src/segment_loss.py:97-121 for ALL sampled segment pairs of a batch in one
-    launch (csrc/fused.hip): flat (rows,128) unit-row embedding, ia / ib (P,num) row indices of the
+    launch (csrc/fused.hip): flat (rows,D) unit-row embedding, D = 32, 64 or 128, ia / ib (P,num) row indices of the
     anchor-positive / negative samples, w (P,) = 1 / (pairs of the shape + 1e-8) -> sum over the
     items of w * (sum_ij c_ij - sum_i c_ii) / (#(c > 0) + 1), the count detached like the reference."""
 
@@ -133,10 +143,16 @@ class EmbeddingLoss:
             ib = h2d(np.concatenate(ib, 0), dev)
             wts = h2d(np.concatenate(wts, 0), dev)
             flat = out.reshape(B * N, -1)
-            if FUSED and flat.is_cuda and flat.shape[1] == 128 and num <= 32:
-                loss_diff = loss_diff + _TripletItems.apply(flat, ia, ib, wts, float(self.margin))
+            W = triplet_width(flat.shape[1])
+            if FUSED and flat.is_cuda and W is not None and num <= 32:
+                # widths between the kernels' are zero-padded to the next one: the squared difference of two zero
+                # columns is zero, and the pad hands the gradient's first D columns back
+                global CALLS_TRIPLET_FUSED
+                CALLS_TRIPLET_FUSED += 1
+                flat_w = flat if W == flat.shape[1] else F.pad(flat, (0, W - flat.shape[1]))
+                loss_diff = loss_diff + _TripletItems.apply(flat_w, ia, ib, wts, float(self.margin))
                 continue
-            # other embedding sizes: the same arithmetic as tensor expressions
+            # embeddings wider than 128: the same arithmetic as tensor expressions
             p1, p2 = flat[ia], flat[ib]                              # (P,num,D)
             anchor = p1.unsqueeze(2)
             diff_pos = ((anchor - p1.unsqueeze(1)) ** 2).sum(3)      # (P,num,num)

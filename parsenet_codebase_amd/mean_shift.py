@@ -69,8 +69,12 @@ LAST_NEAREST = None
 # Embedding widths other than 128.  Widths 32 and 64 have kernels of their own
 # (csrc/meanshift_w.hip: bf16 x 3 arithmetic, dense launches, recompute backward); every other width
 # D <= 128 is zero-padded to the next of 32 / 64 / 128 — zero columns are exact in every product and
-# stay zero through the renormalisation — and sliced on the way out.  The block-sparse plans, the
-# locality order and the centre-rows backward stay 128-only.  PARSENET_MS_NARROW: "native" (default) /
+# stay zero through the renormalisation — and sliced on the way out.  The block-sparse plans and the
+# locality order stay 128-only; the forward-only state and its centre-rows backward (csrc/meanshift_rows.hip)
+# run at 32, 64 and 128, and the callers that use them (fitting_batch._fitting_stage, fitting_eval.cluster_shapes)
+# pad once themselves and stay at the kernel width through NMS and memberships.  The embedding loss pads to the
+# next of 32 / 64 / 128 whatever this switch says (losses.triplet_width: its kernels are plain fp32 at every
+# width).  PARSENET_MS_NARROW: "native" (default) /
 # "pad128": every width below 128 zero-padded to 128 and run on the 128-wide path (the A/B of
 # tools/meanshift_width_ab.py, profiles/meanshift_width_ab.txt).  The narrow kernels are bf16 x 3 only:
 # with PARSENET_MS_ARITH = f32 / fp16x2 narrow widths are padded to 128 as well, so the arithmetic asked
@@ -444,7 +448,9 @@ class MeanShiftState:
 def mean_shift_iterations_state(X, b, iterations):
     """The iterations WITHOUT an autograd graph: returns (new_X (B,N,D) detached, state).  The training
     path reads the final iterate at the cluster centres only; ``centre_rows(X, state, ids)`` returns those
-    rows WITH the gradient path back to X."""
+    rows WITH the gradient path back to X.  D is a width the kernels run at as it is (``kernel_width(D) == D``:
+    128, and 32 / 64 on the width kernels); nothing is padded here — the caller pads once and keeps the padded
+    tensor for ``centre_rows`` and everything after it."""
     require_cuda(X)
     if X.dim() != 3:
         raise ValueError("mean_shift_iterations_state expects (B,N,D)")
@@ -506,7 +512,7 @@ class _CentreRows(torch.autograd.Function):
 
 def centre_rows(X, state, ids):
     """Rows ``ids`` (B,R) of the final iterate of ``mean_shift_iterations_state(X, ...)`` with the gradient
-    path to X (R <= 64; ids may repeat)."""
+    path to X (R <= 64; ids may repeat; X as it was handed to ``mean_shift_iterations_state``: width 32, 64 or 128)."""
     if ids.shape[1] > 64:
         raise ValueError("centre_rows: at most 64 rows per batch item, got %d" % ids.shape[1])
     return _CentreRows.apply(X, state, ids)
