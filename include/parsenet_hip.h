@@ -682,6 +682,22 @@ int pn_adam_flat_f32(float* p, const float* g, float* m, float* v, long long n, 
 int pn_gather_flat_f32(const float* const* srcs, const long long* offs, const long long* ns, int count, float* flat,
                        void* stream);
 
+/* ---- linear sum assignment: batched forward auction with eps-scaling (evaluation-mode LS refit) ------
+ * Replaces the solver behind lapsolver.solve_dense in src/primitive_forward.py:197-198, 272-273 up to eps: S
+ * independent problems in one launch, one workgroup each.  Problem s: cost matrix h_cost[s] (a DEVICE pointer; the
+ * four h_* tables are HOST arrays of S entries), h_n[s] rows, h_m[s] >= h_n[s] columns, row stride h_ld[s] >= h_m[s]
+ * doubles, minimised; it is solved as the square h_m x h_m problem with h_m - h_n zero-cost rows (not materialised).
+ * Schedule: eps = max(eps_start, eps_final) x (max - min of the costs), divided by theta > 1 per phase down to
+ * eps_final x that range; assignments are reset between phases, prices kept.  At most max_rounds bidding rounds.
+ * Outputs, out_ld >= every h_m:  col (S,out_ld) int32 — column of row i for i < h_m[s] (rows >= h_n[s] are the
+ * zero-cost rows), -1 where unassigned or beyond h_m[s];  price (S,out_ld) column prices p >= 0;  eps (S) the eps
+ * reached;  rounds (S);  status (S): 0 = complete, then c[i,col_i] + p[col_i] <= min_j (c[i,j] + p[j]) + eps for every
+ * row of the square problem; 1 = stopped by max_rounds with the prices and the partial assignment it had.
+ * Bit-reproducible from run to run.  Limits: h_m <= 3584 (44 bytes of LDS per column). */
+int pn_lsa_auction_f64(const double* const* h_cost, const int* h_n, const int* h_m, const int* h_ld, int S,
+                       double eps_start, double theta, double eps_final, int max_rounds, int out_ld, int* col,
+                       double* price, double* eps, int* rounds, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

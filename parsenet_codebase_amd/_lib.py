@@ -21,7 +21,7 @@ c_size_t = ctypes.c_size_t
 c_double = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/parsenet_hip.h one to one
-ABI_VERSION = 20  # pn_abi_version() of the library these signatures describe
+ABI_VERSION = 21  # pn_abi_version() of the library these signatures describe
 
 SIGNATURES = {
     "pn_last_error": (ctypes.c_char_p, []),
@@ -189,6 +189,8 @@ SIGNATURES = {
     "pn_weighted_max_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_void_p]),
     "pn_affine_act_fwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p]),
     "pn_affine_act_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p]),
+    "pn_lsa_auction_f64": (c_int, [c_void_p] * 4 + [c_int, c_double, c_double, c_double, c_int, c_int] +
+                           [c_void_p] * 5 + [c_void_p]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 
+from . import assignment
 from . import kernels as K
 from ._lib import h2d, require_cuda
 from .bspline import sample_points_from_control_points_, uniform_knot_bspline
@@ -524,7 +525,9 @@ def _refit_spline(control_points, size_u, size_v, input_points, up_range, subsam
     # (1600, M) fp64 on the GPU, from coordinate differences (the GEMM form of cdist loses the
     # digits the assignment's near-ties depend on)
     dist = torch.cdist(samples, inp, compute_mode="donot_use_mm_for_euclid_dist")
-    rids, cids = solve_dense(dist.cpu().numpy())
+    # PARSENET_REFIT_LSA: host (scipy on the downloaded matrix) or device (auction + exact finish), one helper for
+    # this per-segment form and the batched stage
+    cids = assignment.refit_submit(dist, lambda cost: lambda: solve_dense(cost)[1])()
     matched = inp[torch.from_numpy(np.asarray(cids)).to(dev)]
     ku2, kv2 = uniform_knots(new_cp_size, new_degree), uniform_knots(new_cp_size, new_degree)
     NU = torch.from_numpy(basis_matrix(parameters[:, 0], new_cp_size, new_degree, ku2)).to(dev)

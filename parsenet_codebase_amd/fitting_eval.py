@@ -32,6 +32,7 @@ import torch
 from torch.profiler import record_function
 
 from . import _lsa_worker
+from . import assignment
 from . import kernels as K
 from . import mean_shift as MSM
 from ._lib import h2d
@@ -489,6 +490,9 @@ def _refit_draws(kind, a_max):
 # assignment pool: the Hungarian matchings of a batch's refits side by side
 # ---------------------------------------------------------------------------------------------
 _LSA_POOL = None
+# matchings of the LS refit by the path that solved them (PARSENET_REFIT_LSA = host | device; "capped": the device
+# auction hit its round cap and the problem went to the host solver)
+CALLS_LSA = assignment.CALLS_LSA
 REFIT_POOL = os.environ.get("PARSENET_REFIT_POOL", "1") != "0"
 
 
@@ -558,6 +562,11 @@ def _refit_submit(kind, js, spl_segs, draws, P, ctrl, affine, rec):
     off = np.concatenate([[0], np.cumsum(cnt)])
     out = rec.clone()
     pool = assignment_pool()
+
+    def host_submit(cost):
+        if pool is not None:
+            return pool.submit(_lsa_worker.solve, cost).result
+        return lambda: solve_dense(cost)[1]
     pending = []
     for q, t in enumerate(todo):
         d = draws[js[t]]["refit"]
@@ -570,13 +579,13 @@ def _refit_submit(kind, js, spl_segs, draws, P, ctrl, affine, rec):
             inp = inp[h2d(d["sub"], dev)]
         inp = inp.double()
         dist = torch.cdist(samples, inp, compute_mode="donot_use_mm_for_euclid_dist")
-        cost = dist.cpu().numpy()
-        job = pool.submit(_lsa_worker.solve, cost) if pool is not None else None
-        pending.append((t, parameters, inp, cost, job))
+        # PARSENET_REFIT_LSA=device: the matrix stays on the GPU and joins the batch's ONE auction launch, which the
+        # first finish() of either kind triggers (assignment.queue_device)
+        pending.append((t, parameters, inp, assignment.refit_submit(dist, host_submit)))
 
     def finish():
-        for t, parameters, inp, cost, job in pending:
-            cids = job.result() if job is not None else solve_dense(cost)[1]
+        for t, parameters, inp, matching in pending:
+            cids = matching()
             matched = inp[h2d(np.asarray(cids), dev)]
             NU = torch.from_numpy(basis_matrix(parameters[:, 0], 10, cfg["degree"], ku2)).to(dev)
             NV = torch.from_numpy(basis_matrix(parameters[:, 1], 10, cfg["degree"], ku2)).to(dev)
