@@ -698,6 +698,40 @@ int pn_lsa_auction_f64(const double* const* h_cost, const int* h_n, const int* h
                        double eps_start, double theta, double eps_final, int max_rounds, int out_ld, int* col,
                        double* price, double* eps, int* rounds, int* status, void* stream);
 
+/* ---- trimmed surfaces of the evaluation mode (csrc/surface.hip) ------------------------------------------------
+ * Grid occupancy: replaces the loop of src/fitting_utils.py:240-273 (create_grid) for the S fitted segments of a
+ * shape in one launch.  Segment s: a regular size_u[s] x size_v[s] grid of vertices, rows voff[s] .. of grid
+ * (sum U V, 3) fp32, row-major; its up-sampled cloud, rows coff[s] .. coff[s+1] of cloud (sum P, 3) fp32; a threshold.
+ * mask (sum (U-1)(V-1)) bytes, the cells of segment s row-major from cell_off[s]:
+ *   centre = (((v[i][j] + v[i][j+1]) + v[i+1][j]) + v[i+1][j+1]) * 0.25f   per coordinate,
+ *   d      = ((dx*dx + dy*dy) + dz*dz)                                      every operation rounded to fp32 once,
+ *   mask   = sqrtf(min over the cloud of d) < thres[s]                      (a NaN distance never hits),
+ * the decision of the tensor expression bit for bit (the kernel stops at the first hit).  A workgroup owns
+ * pn_grid_occupancy_tile() cells of one segment: tile_off (S+1) is the prefix sum of ceil(cells / tile) and
+ * total_tiles its last entry.  All tables are DEVICE arrays of int32 (thres: fp32).
+ * Limits: size_u, size_v >= 2; every cloud has at least one point; int32 offsets (sum U V, sum P < 2^31 / 3). */
+int pn_grid_occupancy_tile(void);
+int pn_grid_occupancy_ragged_f32(const float* grid, const int* size_u, const int* size_v, const int* voff,
+                                 const float* cloud, const int* coff, const float* thres, const int* tile_off,
+                                 const int* cell_off, int S, int total_tiles, unsigned char* mask, void* stream);
+/* Triangles of the kept cells and area-weighted samples (src/fitting_utils.py:276-303 tessalate_points_fast,
+ * src/utils.py:123-178 sample_mesh / triangle_area_multi), float64 on the widened fp32 vertices, M meshes in one
+ * launch.  Mesh m: grid rows from voff[m], row length size_v[m]; its faces are face_off[m] .. face_off[m+1]
+ * (face_off (M+1), two per kept cell); cells (total_faces / 2) int32: the kept cells of all meshes, row-major index
+ * into the mesh's (U-1) x (V-1) cells, ascending.  Face 2c is (i,j),(i+1,j),(i+1,j+1), face 2c+1 is
+ * (i,j),(i+1,j+1),(i,j+1).
+ *   area: area[f] = 0.5 |(v2 - v1) x (v3 - v1)|.
+ *   sample: sample k of mesh m (samp_off (M+1), every mesh at least one sample) takes the first face of the mesh
+ *   whose cdf (total_faces, per mesh ascending, last entry 1) exceeds pick[k]; (u, v) -> (1-u, 1-v) when u + v > 1;
+ *   out[k] = (float)(v1*u + v2*v + (1 - (u+v))*v3).  face (total_samples) int32, optional: the face taken, local
+ *   to the mesh.  pick, u, v: caller-supplied uniforms in [0, 1), float64. */
+int pn_trimesh_area_f64(const float* grid, const int* voff, const int* size_v, const int* face_off, const int* cells,
+                        int M, int total_faces, double* area, void* stream);
+int pn_trimesh_sample_f64(const float* grid, const int* voff, const int* size_v, const int* face_off,
+                          const int* cells, const double* cdf, const int* samp_off, const double* pick,
+                          const double* u, const double* v, int M, int total_samples, float* out, int* face,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -690,22 +690,39 @@ class FittingModule:
     def forward_pass_plane(self, points, normals, weights, ids, sample_points=False):
         axis, distance = self.fitting.fit_plane_torch(points=points, normals=normals, weights=weights, ids=ids)
         self.fitting.parameters[ids] = ["plane", axis.reshape((3, 1)), distance]
-        return None
+        if not sample_points:
+            return None
+        # src/fitting_optimization.py:165-176: a 120 x 120 grid around the mean of the projected points
+        from . import surface
+        new_points = project_to_plane(points, axis, distance.item())
+        return surface.sample_plane(distance.item(), axis.data.cpu().numpy(),
+                                    mean=torch.mean(new_points, 0).data.cpu().numpy())
 
     def forward_pass_cone(self, points, normals, weights, ids, sample_points=False):
         apex, axis, theta = self.fitting.fit_cone_torch(points, normals, weights=weights, ids=ids)
         self.fitting.parameters[ids] = ["cone", apex.reshape((1, 3)), axis.reshape((3, 1)), theta]
-        return None
+        if not sample_points:
+            return None
+        from . import surface
+        return surface.sample_cone_trim(apex.data.cpu().numpy().reshape(3), axis.data.cpu().numpy().reshape(3),
+                                        theta.item(), points.data.cpu().numpy())
 
     def forward_pass_cylinder(self, points, normals, weights, ids, sample_points=False):
         a, center, radius = self.fitting.fit_cylinder_torch(points, normals, weights, ids=ids)
         self.fitting.parameters[ids] = ["cylinder", a, center, radius]
-        return None
+        if not sample_points:
+            return None
+        from . import surface
+        return surface.sample_cylinder_trim(radius.item(), center.data.cpu().numpy().reshape(3),
+                                            a.data.cpu().numpy().reshape(3), points.data.cpu().numpy())
 
     def forward_pass_sphere(self, points, normals, weights, ids, sample_points=False):
         center, radius = self.fitting.fit_sphere_torch(points, normals, weights, ids=ids)
         self.fitting.parameters[ids] = ["sphere", center, radius]
-        return None
+        if not sample_points:
+            return None
+        from . import surface
+        return surface.sample_sphere(radius.item(), center.data.cpu().numpy())
 
 
 def _mask_index(mask, device):
@@ -718,6 +735,8 @@ _CLOSED_TYPES, _OPEN_TYPES = (0, 9, 6, 7), (2, 8)
 _ANALYTIC = {1: "forward_pass_plane", 3: "forward_pass_cone", 4: "forward_pass_cylinder", 5: "forward_pass_sphere"}
 # evaluation mode re-samples a spline segment into the range its SplineNet was trained on (:989-996, :1030-1036)
 _RESAMPLE = {"closed": (1400, 1800), "open": (1000, 1500)}
+_NO_REFIT_GRIDS = ("sample_points=True with if_optimize=True is not provided: the trimmed surfaces of the LS refit "
+                   "(its own sample grids) are not built; call with if_optimize=False")
 
 
 def fit_one_shape_torch(data, fitter, weights, bw, eval=False, sample_points=False, if_optimize=False,
@@ -729,10 +748,12 @@ def fit_one_shape_torch(data, fitter, weights, bw, eval=False, sample_points=Fal
     (splines: 100) are recorded as None; the ground-truth modal type selects the fit.
     Evaluation mode: the segment's own points with their (hard) weights; spline segments lose their
     statistical outliers and are re-sampled into the SplineNet's range; ``if_optimize`` adds the LS
-    refit (closed: only for segments of more than 200 points)."""
-    if sample_points or if_visualize:
-        raise NotImplementedError("sample_points / if_visualize build open3d meshes for the viewer: out of "
-                                  "scope of the hot path (SURVEY section 8)")
+    refit (closed: only for segments of more than 200 points).
+    ``sample_points``: the analytic fits also return the regular grid on their surface (surface.py: numpy,
+    float64; the plane's takes two draws of numpy's global stream).  ``if_visualize`` (:1038-1044): the ground
+    truth points of a segment are passed on as a tensor on the segment's device."""
+    if sample_points and if_optimize:
+        raise NotImplementedError(_NO_REFIT_GRIDS)
     fitter.fitting.parameters = {}
     gt_points, reconstructed_shape = {}, []
     splines_seen = 0
@@ -760,7 +781,8 @@ def fit_one_shape_torch(data, fitter, weights, bw, eval=False, sample_points=Fal
             fitter.fitting.parameters[label_index] = None
             continue
         if kind == "analytic":
-            rec = getattr(fitter, _ANALYTIC[seg_type])(points, normals, weight, ids=label_index)
+            rec = getattr(fitter, _ANALYTIC[seg_type])(points, normals, weight, ids=label_index,
+                                                       sample_points=sample_points)
         else:
             if eval:
                 size_in = points.shape[0]
@@ -772,6 +794,8 @@ def fit_one_shape_torch(data, fitter, weights, bw, eval=False, sample_points=Fal
             else:
                 rec = fitter.forward_pass_open_spline(points, weights=weight, ids=label_index,
                                                       if_optimize=if_optimize)
+        if if_visualize and gpoints is not None and not torch.is_tensor(gpoints):
+            gpoints = torch.from_numpy(np.asarray(gpoints)).to(points.device)
         gt_points[label_index] = gpoints
         reconstructed_shape.append(rec)
     return gt_points, reconstructed_shape
@@ -1056,11 +1080,14 @@ class Evaluation:
         """src/residual_utils.py:210-331: residual error with HARD memberships.  Every predicted
         segment is fitted on its own points with the modal predicted primitive type (smallest on
         ties, scipy.stats.mode), splines after outlier removal and re-sampling; distances are
-        reported with sqrt=True.  Returns (Loss, parameters, None); the mesh output of
-        ``sample_points`` / ``if_visualize`` is viewer code and not provided."""
-        if sample_points or if_visualize:
-            raise NotImplementedError("sample_points / if_visualize build open3d meshes for the viewer: out "
-                                      "of scope of the hot path (SURVEY section 8)")
+        reported with sqrt=True.  Returns (Loss, parameters, None).
+        ``if_visualize`` (:250-274, :317-325): every predicted segment is kept (the matched ground-truth one may be
+        empty), its own points stand in for the ground truth, and Loss is [].  ``sample_points``: the third result is
+        the list of trimmed surfaces (surface.TrimmedSurface, one per fitted segment; ``epsilon`` overrides the
+        per-type occupancy thresholds) that segment_utils.sample_from_collection_of_mesh samples — test.py:126-168.
+        Together with ``if_optimize`` it raises NotImplementedError."""
+        if sample_points and if_optimize:
+            raise NotImplementedError(_NO_REFIT_GRIDS)
         if not isinstance(cluster_ids, np.ndarray):
             cluster_ids = cluster_ids.data.cpu().numpy()
         labels = np.asarray(labels)
@@ -1071,11 +1098,11 @@ class Evaluation:
         for index, i in enumerate(unique_pred):
             gt_indices_i = labels == cols[index]
             pred_indices_i = cluster_ids == i
-            if (np.sum(gt_indices_i) == 0) or (np.sum(pred_indices_i) == 0):
+            if np.sum(pred_indices_i) == 0 or (np.sum(gt_indices_i) == 0 and not if_visualize):
                 continue
             seg_type = int(np.bincount(pred_primitives[pred_indices_i].astype(np.int64)).argmax())
             pi = _mask_index(pred_indices_i, dev)
-            gi = _mask_index(gt_indices_i, dev)
+            gi = pi if if_visualize else _mask_index(gt_indices_i, dev)
             data.append([points[pi], normals[pi], seg_type, points[gi], pred_indices_i, (index, i)])
         # hard memberships: one-hot of the cluster ids, pushed through the same normalisation and
         # arg-max as the reference does (a fixed point for one-hot input, kept for fidelity)
@@ -1083,10 +1110,17 @@ class Evaluation:
         w = torch.transpose(weights_normalize(w_first, float(bw)), 1, 0)
         w = to_one_hot(torch.max(w, 1)[1], w.shape[1], device_id=dev.index)
         gt_points, recon_points = fit_one_shape_torch(data, self.fitter, w, bw, eval=True,
-                                                      sample_points=False, if_optimize=if_optimize)
-        distance = self.res_loss.residual_loss(gt_points, self.fitter.fitting.parameters, sqrt=True)
-        Loss = self.separate_losses(distance, gt_points, lamb=lamb)
-        return Loss, self.fitter.fitting.parameters, None
+                                                      sample_points=sample_points, if_optimize=if_optimize,
+                                                      if_visualize=if_visualize)
+        Loss = []
+        if not if_visualize:
+            distance = self.res_loss.residual_loss(gt_points, self.fitter.fitting.parameters, sqrt=True)
+            Loss = self.separate_losses(distance, gt_points, lamb=lamb)
+        pred_meshes = None
+        if sample_points:
+            from . import surface
+            pred_meshes = surface.trimmed_surfaces(data, recon_points, epsilon)
+        return Loss, self.fitter.fitting.parameters, pred_meshes
 
     def separate_losses(self, distance, gt_points, lamb=1.0):
         Loss, geometric_loss, spline_loss = [], [], []

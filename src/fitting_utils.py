@@ -12,3 +12,5 @@ from parsenet_codebase_amd.fitting import (EPS, CustomSVD, LeastSquares, best_la
                                            up_sample_points_torch_in_range,
                                            up_sample_points_torch_memory_efficient, weights_normalize)
 from parsenet_codebase_amd.metrics import matching_iou, relaxed_iou  # noqa: F401,E402  (src/fitting_utils.py:18-19)
+from parsenet_codebase_amd.surface import (TrimmedSurface, bit_mapping_points_torch,  # noqa: F401,E402
+                                           visualize_bit_mapping_shape)

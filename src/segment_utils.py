@@ -5,3 +5,4 @@ from parsenet_codebase_amd.metrics import (SIOU, cluster_prob, cluster_prob_mutu
                                            dot_product_from_cluster_centers, iou_segmentation,
                                            matching_iou, mean_IOU_one_sample, primitive_type_segment,
                                            primitive_type_segment_torch, relaxed_iou)
+from parsenet_codebase_amd.surface import sample_from_collection_of_mesh  # noqa: F401,E402
