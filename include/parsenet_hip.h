@@ -732,6 +732,34 @@ int pn_trimesh_sample_f64(const float* grid, const int* voff, const int* size_v,
                           const double* u, const double* v, int M, int total_samples, float* out, int* face,
                           void* stream);
 
+/* ---- point coverage of the fitted primitives (csrc/cover.hip) --------------------------------------------------
+ * Replaces src/eval_utils.py:103-127 (p_coverage: one residual call per primitive over the whole cloud, stack,
+ * minimum) for the B shapes of a ragged batch in one launch.  Shape b: points pt_off[b] .. pt_off[b+1] of points
+ * (T,3) fp32 and primitives prim_off[b] .. prim_off[b+1].  Primitive s: prim_type[s] and the row prim_par[s]
+ * (16 fp32 slots, the layout of pn_primitive_residual_f32):
+ *   0 plane a(3), d;  1 sphere centre(3), r;  2 cylinder axis(3), centre(3), r;  3 cone apex(3), axis(3), theta;
+ *   >= 4 sampled (the two spline kinds): rows samp_off[s] .. samp_off[s+1] of samp (sum, 3) fp32, at least one; the
+ *   parameter row is not read.  samp_off (S+1) is ascending with empty slices for the analytic primitives; samp
+ *   may be NULL when no primitive is sampled.
+ * Per point:  dmin (T) fp32 = the smallest distance over the shape's primitives, each with guard_sqrt
+ * (sqrtf(max(d, 1e-5f))): analytic ones by the fp32 arithmetic of the batched fitting stage; for a sampled one the
+ * nearest sample j is the first arg-min of ((dx*dx + dy*dy) + dz*dz) (the Chamfer kernel's chain, every operation
+ * rounded once) and the distance is sqrtf(max(((dx*dx + dz*dz) + dy*dy) at j, 1e-5f)) — the order in which the
+ * tensor library's GPU reduction was observed to add the three squares (tools/sum3_order_probe.py,
+ * profiles/sum3_order.txt; pinned bit for bit by tests/test_pcover_gpu.py, not guaranteed by that library), so that
+ * the value is chamfer_distance_single_shape's;
+ * arg (T) int32 = the index of that primitive within the shape, the lowest on equal values.  A NaN distance is kept
+ * (the first one; a point with a NaN coordinate gets NaN from sampled primitives too: they re-evaluate at sample 0
+ * when no comparison held); a shape without primitives, or a point whose distances are all inf, gets (inf, -1).
+ * A workgroup owns pn_point_primitive_min_tile() consecutive points of one shape: tile t starts at point
+ * tile_first[t] (a row of points) of shape tile_shape[t]; total_tiles = sum_b ceil(N_b / tile).  All tables are
+ * DEVICE arrays of int32.  The result of a point does not depend on the tiling.
+ * Limits: int32 offsets (T, sum of samples < 2^31 / 3). */
+int pn_point_primitive_min_tile(void);
+int pn_point_primitive_min_f32(const float* points, const int* pt_off, const int* prim_off, const int* prim_type,
+                               const float* prim_par, const float* samp, const int* samp_off, const int* tile_shape,
+                               const int* tile_first, int B, int total_tiles, float* dmin, int* arg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

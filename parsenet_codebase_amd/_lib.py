@@ -21,7 +21,7 @@ c_size_t = ctypes.c_size_t
 c_double = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/parsenet_hip.h one to one
-ABI_VERSION = 22  # pn_abi_version() of the library these signatures describe
+ABI_VERSION = 23  # pn_abi_version() of the library these signatures describe
 
 SIGNATURES = {
     "pn_last_error": (ctypes.c_char_p, []),
@@ -195,6 +195,8 @@ SIGNATURES = {
     "pn_grid_occupancy_ragged_f32": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p]),
     "pn_trimesh_area_f64": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
     "pn_trimesh_sample_f64": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pn_point_primitive_min_tile": (c_int, []),
+    "pn_point_primitive_min_f32": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -19,4 +19,5 @@ extern "C" const char* pn_last_error(void) { return g_err; }
 // 20: the kernel profile as an argument (pn_meanshift_*_iter_*_kind_f32: Gaussian / Epanechnikov)
 // 21: linear sum assignment on the device (pn_lsa_auction_f64)
 // 22: trimmed surfaces (pn_grid_occupancy_ragged_f32, pn_trimesh_area_f64, pn_trimesh_sample_f64)
-extern "C" int pn_abi_version(void) { return 22; }
+// 23: point coverage of the fitted primitives (pn_point_primitive_min_f32)
+extern "C" int pn_abi_version(void) { return 23; }

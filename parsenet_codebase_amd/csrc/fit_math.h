@@ -613,3 +613,41 @@ FB_HD Df residual_point(int type, float px, float py, float pz, const float* th,
   return d;
 }
 
+// The value of residual_point without the tangents: the same fp32 operations in the same order (the .v members of
+// the dual-number expressions above, written out), for callers that need distances only (cover.hip).
+FB_HD float fclampv(float a, float lo, float hi) {
+  if (a < lo) return lo;
+  if (a > hi) return hi;
+  return a;
+}
+FB_HD float fnorm3v(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
+
+FB_HD float residual_point_value(int type, float px, float py, float pz, const float* th, int sqrt_flag) {
+  float d;
+  if (type == FB_PLANE) {
+    const float e = px * th[0] + py * th[1] + pz * th[2] - th[3];
+    d = e * e;
+  } else if (type == FB_SPHERE) {
+    const float e = fnorm3v(px - th[0], py - th[1], pz - th[2]) - th[3];
+    d = e * e;
+  } else if (type == FB_CYLINDER) {
+    const float vx = px - th[3], vy = py - th[4], vz = pz - th[5];
+    const float prj = vx * th[0] + vy * th[1] + vz * th[2];
+    const float q = fclampv(vx * vx + vy * vy + vz * vz - prj * prj, 1e-5f, __builtin_inff());
+    const float e = sqrtf(q) - th[6];
+    d = e * e;
+  } else {
+    const float vx = px - th[0] + 1e-8f, vy = py - th[1] + 1e-8f, vz = pz - th[2] + 1e-8f;
+    const float mod = fnorm3v(vx, vy, vz);
+    const float ax = fclampv((vx * th[3] + vy * th[4] + vz * th[5]) / (mod + 1e-7f), -0.999f, 0.999f);
+    float da = acosf(ax) - th[6];
+    if (da < 0.f) da = 0.f - da;
+    else if (da == 0.f) da = 0.f;
+    da = fclampv(da, -__builtin_inff(), 3.142f / 2.0f);
+    const float e = mod * sinf(da);
+    d = e * e;
+  }
+  if (sqrt_flag) d = sqrtf(fclampv(d, 1e-5f, __builtin_inff()));   // guard_sqrt
+  return d;
+}
+

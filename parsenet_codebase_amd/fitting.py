@@ -1122,6 +1122,12 @@ class Evaluation:
             pred_meshes = surface.trimmed_surfaces(data, recon_points, epsilon)
         return Loss, self.fitter.fitting.parameters, pred_meshes
 
+    def p_coverage(self, points, parameters):
+        """metrics.p_coverage on the parameters ``residual_eval_mode`` returned: (mean distance of the input points
+        to the nearest fitted primitive, share of them under 0.01)."""
+        from .metrics import p_coverage
+        return p_coverage(points, parameters)
+
     def separate_losses(self, distance, gt_points, lamb=1.0):
         Loss, geometric_loss, spline_loss = [], [], []
         keys = [v for v in sorted(gt_points.keys()) if gt_points[v] is not None]

@@ -1355,3 +1355,58 @@ def weighted_max_bwd(g, idx, val, N):
                                                  current_stream(g.device))
     check(rc, "pn_weighted_max_bwd_f32")
     return gw
+
+
+COVER_SAMPLED = 4   # type ids of pn_point_primitive_min_f32: 0 plane, 1 sphere, 2 cylinder, 3 cone, 4 sampled
+
+
+def point_primitive_min(points, pt_off, prim_off, prim_type, prim_par, samp, samp_off):
+    """Distance of every point to the nearest primitive of its shape (csrc/cover.hip), B shapes in ONE launch.
+    points (T,3), prim_par (S,16), samp (C,3) or None: fp32 on the GPU.  pt_off (B+1), prim_off (B+1), prim_type (S),
+    samp_off (S+1): HOST integer arrays — they are checked here (ascending, inside the arrays they index, a sampled
+    primitive has at least one sample) and uploaded with the tile table in one copy.
+    Returns (dmin (T) fp32, arg (T) int32: index within the shape, lowest on ties; -1 for a shape without primitives)."""
+    import numpy as np
+    require_cuda(points, prim_par, samp)
+    points, prim_par = _f32c(points, "points"), _f32c(prim_par, "prim_par")
+    pt_off, prim_off, prim_type, samp_off = [np.asarray(a, np.int64).reshape(-1)
+                                             for a in (pt_off, prim_off, prim_type, samp_off)]
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("point_primitive_min expects (T,3) points, got %s" % (tuple(points.shape),))
+    T, S, B = points.shape[0], prim_type.shape[0], pt_off.shape[0] - 1
+    C = 0
+    if samp is not None:
+        samp = _f32c(samp, "samp")
+        if samp.dim() != 2 or samp.shape[1] != 3:
+            raise ValueError("point_primitive_min expects (C,3) samples, got %s" % (tuple(samp.shape),))
+        C = samp.shape[0]
+    if B < 1 or T < 1 or S < 1 or prim_off.shape[0] != B + 1 or samp_off.shape[0] != S + 1 or tuple(prim_par.shape) != (S, FIT_NPAR):
+        raise ValueError("point_primitive_min: tables of %d shapes, %d points and %d primitives do not fit together"
+                         % (B, T, S))
+    for name, off, end in (("pt_off", pt_off, T), ("prim_off", prim_off, S), ("samp_off", samp_off, C)):
+        if off[0] != 0 or off[-1] != end or (np.diff(off) < 0).any():
+            raise ValueError("point_primitive_min: %s must ascend from 0 to %d" % (name, end))
+    if (prim_type < 0).any() or (prim_type > COVER_SAMPLED).any():
+        raise ValueError("point_primitive_min: type ids are 0 .. %d" % COVER_SAMPLED)
+    if (np.diff(samp_off)[prim_type == COVER_SAMPLED] < 1).any():
+        raise ValueError("point_primitive_min: a sampled primitive without samples")
+    if max(T, C) * 3 >= 2 ** 31:
+        raise ValueError("point_primitive_min: int32 offsets")
+    lib = _lib.load()
+    dev = points.device
+    tile = lib.pn_point_primitive_min_tile()
+    n = np.diff(pt_off)
+    tiles = (n + tile - 1) // tile
+    tile_shape = np.repeat(np.arange(B), tiles)
+    tile_first = pt_off[tile_shape] + (np.arange(int(tiles.sum())) - np.repeat(np.cumsum(tiles) - tiles, tiles)) * tile
+    table = _lib.h2d(np.concatenate([pt_off, prim_off, prim_type, samp_off, tile_shape, tile_first]).astype(np.int32), dev)
+    o = np.cumsum([0, B + 1, B + 1, S, S + 1, tile_shape.shape[0]])
+    col = [table[o[i]:o[i + 1] if i + 1 < len(o) else None] for i in range(len(o))]
+    dmin = torch.empty(T, dtype=torch.float32, device=dev)
+    arg = torch.empty(T, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        rc = lib.pn_point_primitive_min_f32(ptr(points), ptr(col[0]), ptr(col[1]), ptr(col[2]), ptr(prim_par), ptr(samp),
+                                            ptr(col[3]), ptr(col[4]), ptr(col[5]), B, int(tile_shape.shape[0]),
+                                            ptr(dmin), ptr(arg), current_stream(dev))
+    check(rc, "pn_point_primitive_min_f32")
+    return dmin, arg

@@ -1,10 +1,15 @@
 """Evaluation metrics of the reference's test.py:39-47, 157-185 on the HIP Chamfer kernel:
 surface coverage (s-k), point coverage (p-k), their thresholds at 1 % and 2 % of the unit box,
 and the symmetric Chamfer figure the paper reports; plus segment / primitive-type IoU
-(``SIOU_matched_segments``) and the per-point primitive mIoU (``evaluate_miou``) re-exported."""
+(``SIOU_matched_segments``) and the per-point primitive mIoU (``evaluate_miou``) re-exported; and the point coverage of the fitted
+primitives of src/eval_utils.py:103-127 (``p_coverage``)."""
+import os
+
 import numpy as np
 import torch
 
+from . import kernels as K
+from ._lib import h2d
 from .chamfer import chamfer_distance_single_shape
 from .fitting import SIOU_matched_segments  # noqa: F401
 from .losses import evaluate_miou  # noqa: F401
@@ -108,3 +113,178 @@ def cluster_prob_mutual(embedding, centers, bandwidth, if_normalize=False):
         prob = prob - np.min(prob, 1, keepdims=True)
         prob = prob / np.max(prob, 1, keepdims=True)
     return prob
+
+
+# ---------------------------------------------------------------------------------------
+# src/eval_utils.py: point coverage of the fitted primitives, and its separate_losses
+# ---------------------------------------------------------------------------------------
+# PARSENET_PCOVER: "fused" = all primitives of all shapes in one launch (csrc/cover.hip); "tensor" = the reference's
+# form, one ResidualLoss(one_side=True, reduce=False) call per primitive, stack, min.  fused is opt-in until
+# tools/pcover_ab.py has been run on an MI355X and shows it faster at every size (profiles/pcover_ab.txt).
+DEFAULT_PCOVER = "tensor"
+CALLS_PCOVER = {"fused": 0, "tensor": 0}      # shapes served, by path
+_PCOVER_TYPES = {"plane": (0, 4), "sphere": (1, 4), "cylinder": (2, 7), "cone": (3, 7),
+                 "open-spline": (K.COVER_SAMPLED, 0), "closed-spline": (K.COVER_SAMPLED, 0)}
+
+
+def pcover_path():
+    name = os.environ.get("PARSENET_PCOVER", DEFAULT_PCOVER)
+    if name not in CALLS_PCOVER:
+        raise ValueError("PARSENET_PCOVER must be one of %s, got %r" % (sorted(CALLS_PCOVER), name))
+    return name
+
+
+def _dev32(x, dev):
+    if torch.is_tensor(x):
+        return x.detach().to(device=dev, dtype=torch.float32)
+    return h2d(np.asarray(x, np.float32), dev)
+
+
+def _pcover_tensor(pts, live, residual_cls):
+    """The per-primitive path: (dmin (N,), position of the nearest primitive in ``live``)."""
+    prm = dict(live)
+    dist = residual_cls(one_side=True, reduce=False).residual_loss({k: pts for k in prm}, prm, sqrt=True)
+    dmin, arg = torch.min(torch.stack([v[1] for v in dist.values()], 0), 0)
+    return dmin, arg
+
+
+def _pcover_fused(pts, lives):
+    """pts: list of (N_b,3) fp32 device tensors; lives: per shape the (key, entry) pairs that are not None.
+    ONE launch for every non-torus primitive of every shape; -> per shape (dmin, position in ``live``)."""
+    from .fitting import ComputePrimitiveDistance
+    dev = pts[0].device
+    # The parameter table is packed on the host and uploaded once.  Values that already live on a device are not
+    # downloaded (a synchronisation each): they are concatenated once and put into the table by one indexed
+    # assignment whose positions come from the host.
+    samp, types, nsamp, nprim, slots, torus = [], [], [], [], [], []
+    host_val, host_pos, dev_val, dev_pos = [], [], [], []
+    for b, live in enumerate(lives):
+        pos = []
+        for i, (_, v) in enumerate(live):
+            if v[0] == "torus":                     # no fit and no slot in the kernel: merged after the launch
+                torus.append((b, i, v))
+                continue
+            t, width = _PCOVER_TYPES[v[0]]
+            pos.append(i)
+            at = len(types) * K.FIT_NPAR
+            types.append(t)
+            if t == K.COVER_SAMPLED:
+                c = _dev32(v[1][0], dev).reshape(-1, 3)  # params[0][0]: the samples distance_from_bspline takes
+                samp.append(c)
+                nsamp.append(c.shape[0])
+                continue
+            nsamp.append(0)
+            end = at + width
+            for x in v[1:]:
+                if torch.is_tensor(x) and x.is_cuda:
+                    x = x.detach().reshape(-1)
+                    n = x.numel()
+                    dev_val.append(x.to(device=dev, dtype=torch.float32))
+                    dev_pos.append(np.arange(at, at + n))
+                else:
+                    x = (x.detach().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float32).reshape(-1)
+                    n = x.size
+                    host_val.append(x)
+                    host_pos.append(np.arange(at, at + n))
+                at += n
+            if at != end:
+                raise ValueError("p_coverage: a %s entry with %d parameter values (%d expected)"
+                                 % (v[0], at - (end - width), width))
+        slots.append(pos)
+        nprim.append(len(pos))
+    pt_off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])])
+    if types:
+        table = np.zeros(len(types) * K.FIT_NPAR, np.float32)
+        if host_val:
+            table[np.concatenate(host_pos)] = np.concatenate(host_val)
+        table = h2d(table, dev)
+        if dev_val:
+            table[h2d(np.concatenate(dev_pos).astype(np.int64), dev)] = torch.cat(dev_val)
+        dmin, arg = K.point_primitive_min(
+            pts[0] if len(pts) == 1 else torch.cat(pts), pt_off, np.concatenate([[0], np.cumsum(nprim)]), types,
+            table.reshape(-1, K.FIT_NPAR), torch.cat(samp) if samp else None,
+            np.concatenate([[0], np.cumsum(nsamp)]))
+    else:
+        dmin = torch.full((int(pt_off[-1]),), float("inf"), dtype=torch.float32, device=dev)
+        arg = torch.full((int(pt_off[-1]),), -1, dtype=torch.int32, device=dev)
+    arg = arg.clamp_min(0)                          # (-1: see below)
+    out = []
+    for b, live in enumerate(lives):
+        d, a = dmin[pt_off[b]:pt_off[b + 1]], arg[pt_off[b]:pt_off[b + 1]].long()
+        if len(pts) > 1:
+            # own storage: the order in which torch.mean adds depends on the alignment of the slice, and a shape's
+            # figures must not depend on the batch it was evaluated in
+            d = d.clone()
+        # kernel index -> position in live.  The kernel reports -1 where nothing compared smaller than inf: a shape
+        # without kernel primitives (torus entries only), or distances that are all inf.  -1 is read as kernel index
+        # 0 (torch.min over an all-inf stack also reports its first row), and a shape without kernel primitives
+        # starts at its first entry, so the index stays inside ``live`` even when a torus distance is NaN.
+        if len(slots[b]) != len(live):
+            a = h2d(np.asarray(slots[b] or [0], np.int64), dev)[a]
+        out.append([d, a])
+    cp = ComputePrimitiveDistance(reduce=False, one_side=True)
+    for b, i, v in torus:                           # the lowest position wins on equal values here too
+        d, a = out[b]
+        dt = cp.distance_from_torus(pts[b], v[1:], sqrt=True).reshape(-1)
+        out[b] = [torch.minimum(d, dt), torch.where((dt < d) | ((dt == d) & (i < a)), torch.full_like(a, i), a)]
+    return out
+
+
+def p_coverage_batch(points, parameters_list, return_points=False, ResidualLoss=None):
+    """``p_coverage`` of B shapes; with PARSENET_PCOVER=fused ONE launch serves them all.  points: a list of (N_b,3)
+    arrays or tensors (the shapes may differ in size) or one (B,N,3); parameters_list: one dict per shape.
+    Returns a list of (mean_coverage, cover); with ``return_points`` of (mean_coverage, cover, dmin (N_b,) fp32,
+    key (N_b,) int64: the dict key of the nearest primitive, the earliest entry on equal distances)."""
+    path = pcover_path()
+    lives = []
+    for prm in parameters_list:
+        live = [(k, v) for k, v in prm.items() if v is not None]
+        if not live:
+            raise ValueError("p_coverage: no fitted primitive (an empty dict, or None entries only)")
+        for _, v in live:
+            if v[0] != "torus" and v[0] not in _PCOVER_TYPES:
+                raise ValueError("p_coverage: unknown primitive type %r" % (v[0],))
+        lives.append(live)
+    if not lives or len(points) != len(lives):
+        raise ValueError("p_coverage_batch: %d point clouds for %d parameter dicts" % (len(points), len(lives)))
+    pts = []
+    for p in points:
+        p = torch.from_numpy(np.asarray(p, np.float32)).cuda() if not torch.is_tensor(p) else p.detach().float().cuda()
+        if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError("p_coverage: points must be (N,3), got %s" % (tuple(p.shape),))
+        pts.append(p.contiguous())
+    CALLS_PCOVER[path] += len(lives)
+    if path == "fused":
+        res = _pcover_fused(pts, lives)
+    else:
+        if ResidualLoss is None:
+            from .fitting import ResidualLoss
+        res = [_pcover_tensor(p, live, ResidualLoss) for p, live in zip(pts, lives)]
+    out = []
+    for (dmin, arg), live in zip(res, lives):
+        row = (torch.mean(dmin), torch.mean((dmin < 0.01).float()))
+        if return_points:
+            keys = [k for k, _ in live]
+            if not all(isinstance(k, (int, np.integer)) for k in keys):
+                raise TypeError("p_coverage_batch(return_points=True) needs integer dict keys")
+            row = row + (dmin, h2d(np.asarray(keys, np.int64), dmin.device)[arg])
+        out.append(row)
+    return out
+
+
+def p_coverage(points, parameters, ResidualLoss=None):
+    """eval_utils.py:103-127: for every input point the distance to the nearest predicted primitive (analytic for
+    plane, sphere, cylinder, cone and torus, sample-based for the splines; sqrt=True).  points (N,3) numpy array or
+    tensor; parameters: the dict fitter.fitting.parameters / residual_eval_mode returns (None entries are skipped;
+    none left raises ValueError where the reference fails in torch.stack).  ``ResidualLoss``: the reference passes
+    its class; the per-primitive path (PARSENET_PCOVER=tensor) uses it when given.
+    Returns (mean_coverage, cover): the mean distance and the share of points under 0.01, 0-d tensors."""
+    return p_coverage_batch([points], [parameters], ResidualLoss=ResidualLoss)[0]
+
+
+def separate_losses(distance, gt_points, lamb=1.0):
+    """eval_utils.py:130-175: Evaluation.separate_losses, which here also skips the segments with fewer than 100
+    ground-truth points."""
+    from .fitting import Evaluation
+    kept = {k: v for k, v in gt_points.items() if v is not None and v.shape[0] >= 100}
+    return Evaluation.separate_losses(None, distance, kept, lamb=lamb)
