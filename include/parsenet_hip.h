@@ -512,6 +512,16 @@ int pn_chamfer_ragged_bwd_f32(const float* pred, const int* offA, int maxA, cons
                               const int64_t* argA, const int64_t* argB, const float* g, int S, float* gpred,
                               void* stream);
 
+/* Coverage figures of test.py:157-180 for S shapes at once: the squared nearest-neighbour minima of both sides
+ * concatenated over the shapes (offA, offB: S+1 ints) -> out (S,6) float64, per side
+ *   sum_i sqrtf(fmaxf(x_i, 1e-5f))   (guard_sqrt, the square root in fp32, the sum in fp64),
+ *   #{i : that root < 0.01f},  #{i : that root < 0.02f}                  (fp32 comparisons);
+ * columns 0-2 side A, 3-5 side B.  One workgroup per (shape, side); every thread adds a strided range in ascending
+ * order, a fixed tree combines the 256 partial sums: no atomics, a shape's row depends on its own values only.  The
+ * means, and cd, are the host's to form (float64). */
+int pn_coverage_reduce_f32(const float* minA, const int* offA, const float* minB, const int* offB, int S, double* out,
+                           void* stream);
+
 /* Gradient of out[b,m,:] = src[b,idx[b,m],:] for rows of 3 floats (the nearest-neighbour gather of
  * src/utils.py:273-358's min over the broadcast): gsrc[b,i,:] = sum_{m: idx[b,m] = i} g[b,m,:] in
  * ascending m, gathered per row — no atomics.  g (B,M,3), idx (B,M), gsrc (B,N,3) fully written. */

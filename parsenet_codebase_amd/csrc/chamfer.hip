@@ -532,6 +532,59 @@ extern "C" int pn_chamfer_ragged_reduce_f32(const float* minA, const int* offA, 
   return PN_OK;
 }
 
+// ---- coverage figures of a batch of shapes (test.py:157-180) -------------------------------------
+// out[s][3 side + {0,1,2}] = sum of guard_sqrt(x), #{root < 0.01f}, #{root < 0.02f} over the side's squared minima.
+// One workgroup per (shape, side).  Square root and comparisons in fp32 (torch.sqrt(torch.clamp(x, min=1e-5)) and
+// ``d < 0.01`` on an fp32 tensor); every thread adds its strided range in ascending order in fp64, the 256 partial
+// sums meet in a fixed tree.  The counts are integers below 2^31 (int32 offsets), exact in a double.
+__global__ __launch_bounds__(256) void pn_coverage_reduce_kernel(const float* __restrict__ minA,
+                                                                 const int* __restrict__ offA,
+                                                                 const float* __restrict__ minB,
+                                                                 const int* __restrict__ offB,
+                                                                 double* __restrict__ out) {
+  __shared__ double rsum[256];
+  __shared__ int rc1[256], rc2[256];
+  const int s = blockIdx.x >> 1, side = blockIdx.x & 1, t = threadIdx.x;
+  const float* __restrict__ x = side ? minB : minA;
+  const int* __restrict__ off = side ? offB : offA;
+  const int i0 = off[s], i1 = off[s + 1];
+  double sum = 0.0;
+  int c1 = 0, c2 = 0;
+  for (int i = i0 + t; i < i1; i += 256) {
+    const float r = sqrtf(fmaxf(x[i], 1e-5f));
+    sum += (double)r;
+    c1 += r < 0.01f;
+    c2 += r < 0.02f;
+  }
+  rsum[t] = sum;
+  rc1[t] = c1;
+  rc2[t] = c2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+      rsum[t] += rsum[t + o];
+      rc1[t] += rc1[t + o];
+      rc2[t] += rc2[t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    double* row = out + (size_t)s * 6 + side * 3;
+    row[0] = rsum[0];
+    row[1] = (double)rc1[0];
+    row[2] = (double)rc2[0];
+  }
+}
+
+extern "C" int pn_coverage_reduce_f32(const float* minA, const int* offA, const float* minB, const int* offB, int S,
+                                      double* out, void* stream_) {
+  PN_CHECK_ARG(minA && offA && minB && offB && out && S > 0 && S < (1 << 30), "pn_coverage_reduce_f32: bad arguments");
+  hipLaunchKernelGGL(pn_coverage_reduce_kernel, dim3(2 * S), dim3(256), 0, (hipStream_t)stream_, minA, offA, minB,
+                     offB, out);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
 // d out / d pred: every minimum routed to its pair of points,
 //   gpred[i] = (pred_i - gt[argA_i]) * g_s / nA  +  sum_{j : argB_j = i} (pred_i - gt_j) * g_s / nB
 // (the 2 of the square cancels the 1/2).  One wave owns 64 prediction rows of an item and walks the

@@ -736,7 +736,8 @@ _ANALYTIC = {1: "forward_pass_plane", 3: "forward_pass_cone", 4: "forward_pass_c
 # evaluation mode re-samples a spline segment into the range its SplineNet was trained on (:989-996, :1030-1036)
 _RESAMPLE = {"closed": (1400, 1800), "open": (1000, 1500)}
 _NO_REFIT_GRIDS = ("sample_points=True with if_optimize=True is not provided: the trimmed surfaces of the LS refit "
-                   "(its own sample grids) are not built; call with if_optimize=False")
+                   "(its own sample grids) are not built here; call with if_optimize=False, or use "
+                   "Evaluation.reconstruct_batch, which provides that combination")
 
 
 def fit_one_shape_torch(data, fitter, weights, bw, eval=False, sample_points=False, if_optimize=False,
@@ -1042,6 +1043,15 @@ class Evaluation:
         require_cuda(embedding, points, normals)
         return fitting_losses_eval(self, embedding, points, normals, labels, primitives, primitives_log_prob,
                                    quantile, iterations, lamb, if_optimize)
+
+    def reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw=0.01,
+                          if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000):
+        """test.py:108-185 for B shapes from given cluster ids: parameters, trimmed surfaces, samples and the table of
+        seg-IoU, type-IoU, s-cover, p-cover and CD per shape, stage by stage (fitting_eval.reconstruct_batch).  The
+        trimmed surfaces of the LS refit (``if_optimize=True``) are available here only."""
+        from .fitting_eval import reconstruct_batch
+        return reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw,
+                                 if_optimize, if_visualize, epsilon, n_samples)
 
     def fitting_losses_pipelined(self, embedding, points, normals, labels, primitives, primitives_log_prob,
                                  quantile=0.125, iterations=5, lamb=1.0, chunks=2):

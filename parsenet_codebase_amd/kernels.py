@@ -1033,6 +1033,24 @@ def chamfer_ragged_reduce(minA, off_a, minB, off_b):
     return out
 
 
+def coverage_reduce(minA, off_a, minB, off_b):
+    """The coverage figures of S shapes from the SQUARED nearest-neighbour minima of both sides (ragged, offsets (S+1,)
+    int32 on the GPU) -> (S,6) float64 on the GPU: per side the fp64 sum of sqrt(clamp(x, 1e-5)) (fp32 roots), the
+    count of roots < 0.01 and the count < 0.02 (fp32 comparisons).  Fixed summation order, no atomics: a shape's row
+    does not depend on the batch around it."""
+    require_cuda(minA, minB, off_a, off_b)
+    off_a, off_b = _i32c(off_a, "off_a"), _i32c(off_b, "off_b")
+    S = off_a.shape[0] - 1
+    if S < 1 or off_b.shape[0] != S + 1:
+        raise ValueError("coverage_reduce: offsets of %d and %d entries" % (off_a.shape[0], off_b.shape[0]))
+    out = torch.empty((S, 6), dtype=torch.float64, device=minA.device)
+    with _lib.on_device(minA.device):
+        rc = _lib.load().pn_coverage_reduce_f32(ptr(_f32c(minA, "minA")), ptr(off_a), ptr(_f32c(minB, "minB")),
+                                                ptr(off_b), S, ptr(out), current_stream(minA.device))
+    check(rc, "pn_coverage_reduce_f32")
+    return out
+
+
 def chamfer_ragged_bwd(pred, off_a, max_a, gt, off_b, argA, argB, g):
     """Gradient of chamfer_ragged_reduce with respect to the predictions (TA,3); g (S,)."""
     require_cuda(pred, gt, g)

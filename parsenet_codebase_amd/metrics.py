@@ -36,6 +36,54 @@ def coverage_metrics(pred_points, points):
             "pk_2": torch.mean((cd2 < 0.02).float()).item(), "pk": pk, "cd": (sk + pk) / 2.0}
 
 
+def coverage_rows(pred, pts):
+    """pred[b] (M_b,3), pts[b] (N_b,3): fp32 tensors on the GPU -> one dict per shape (the keys of
+    ``coverage_metrics``).  ONE ragged nearest-neighbour call for both sides of all shapes, ONE reduction
+    (csrc/chamfer.hip, pn_coverage_reduce_f32: fp32 roots and comparisons, fp64 sums in a fixed order), ONE download
+    of the (S,6) table; means and cd are formed here in float64."""
+    dev = pts[0].device
+    na = np.asarray([p.shape[0] for p in pts], np.int64)
+    nb = np.asarray([p.shape[0] for p in pred], np.int64)
+    if na.sum() >= 2 ** 31 or nb.sum() >= 2 ** 31:
+        raise ValueError("coverage_metrics_batch: int32 offsets")
+    S = na.shape[0]
+    table = h2d(np.concatenate([[0], np.cumsum(na), [0], np.cumsum(nb)]).astype(np.int32), dev)
+    off_a, off_b = table[:S + 1], table[S + 1:]
+    a = pts[0] if S == 1 else torch.cat(pts)
+    b = pred[0] if S == 1 else torch.cat(pred)
+    minA, _, minB, _ = K.chamfer_nn_ragged(a, off_a, int(na.max()), b, off_b, int(nb.max()))
+    t = K.coverage_reduce(minA, off_a, minB, off_b).cpu().numpy()
+    out = []
+    for s in range(S):
+        n, m = float(na[s]), float(nb[s])
+        sk, pk = t[s, 0] / n, t[s, 3] / m
+        out.append({"sk_1": t[s, 1] / n, "sk_2": t[s, 2] / n, "sk": sk, "pk_1": t[s, 4] / m, "pk_2": t[s, 5] / m,
+                    "pk": pk, "cd": (sk + pk) / 2.0})
+    return out
+
+
+def coverage_metrics_batch(pred_points_list, points_list):
+    """``coverage_metrics`` of S shapes — pred_points_list[s] (M_s,3) samples of the reconstructed surfaces,
+    points_list[s] (N_s,3) the input cloud, arrays or tensors — in three launches and one download (coverage_rows).
+    A shape's figures do not depend on the batch it is evaluated in.  Python floats formed in float64: the shares are
+    count / size, the means within the fp32 rounding of torch.mean of ``coverage_metrics``."""
+    if len(pred_points_list) != len(points_list) or len(points_list) < 1:
+        raise ValueError("coverage_metrics_batch: %d sample sets for %d clouds" % (len(pred_points_list),
+                                                                                  len(points_list)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    both = []
+    for name, lst in (("pred_points", pred_points_list), ("points", points_list)):
+        row = []
+        for s, p in enumerate(lst):
+            p = _dev32(p, dev).contiguous()
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+                raise ValueError("coverage_metrics_batch: shape %d: %s must be (N,3) with N >= 1, got %s"
+                                 % (s, name, tuple(p.shape)))
+            row.append(p)
+        both.append(row)
+    return [{k: float(v) for k, v in r.items()} for r in coverage_rows(both[0], both[1])]
+
+
 # ---------------------------------------------------------------------------------------
 # src/segment_utils.py: the remaining segmentation metrics and membership helpers
 # ---------------------------------------------------------------------------------------

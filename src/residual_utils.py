@@ -2,3 +2,4 @@
 evaluation mode with hard memberships)."""
 from parsenet_codebase_amd.fitting import Evaluation  # noqa: F401
 from parsenet_codebase_amd.fitting import one_hot_normalization as convert_to_one_hot  # noqa: F401,E402
+from parsenet_codebase_amd.fitting_eval import reconstruct_batch  # noqa: F401,E402
