@@ -25,6 +25,9 @@
 extern "C" {
 #endif
 
+/* pn_abi_version() of the library this header describes; it changes with every change of a declaration below */
+#define PN_ABI_VERSION 23
+
 #define PN_OK 0
 #define PN_ERR_ARG (-1)
 #define PN_ERR_HIP (-2)

@@ -8,197 +8,69 @@ device pointers are then shared between torch and this library.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must be loaded before the HIP library, see docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libparsenet_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "parsenet_hip.h")
 
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_float = ctypes.c_float
-c_size_t = ctypes.c_size_t
-c_double = ctypes.c_double
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "long long": ctypes.c_longlong}
+_DECLARATION = re.compile(r"([\w\s*]+?)\b(\w+)\s*\((.*)\)", re.S)
+_CONSTANT = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(PN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", re.M)
 
-# name -> (restype, argtypes); mirrors include/parsenet_hip.h one to one
-ABI_VERSION = 23  # pn_abi_version() of the library these signatures describe
 
-SIGNATURES = {
-    "pn_last_error": (ctypes.c_char_p, []),
-    "pn_abi_version": (c_int, []),
-    "pn_prof_enable": (None, [c_int]),
-    "pn_prof_reset": (None, []),
-    "pn_prof_count": (c_int, []),
-    "pn_prof_get": (c_int, [c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_double),
-                            ctypes.POINTER(ctypes.c_longlong)]),
-    "pn_knn_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pn_knn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_knn_pn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_knn_graph_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_knn3_ragged": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "pn_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "pn_edge_feature_fwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_edge_feature_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                        c_size_t, c_void_p]),
-    "pn_edgeconv_reduce_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pn_edgeconv_reduce_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p]),
-    "pn_edgeconv_reduce_fwd_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p]),
-    "pn_moments_f32": (c_int, [c_void_p, c_int, c_double, c_float, c_void_p, c_void_p, c_void_p]),
-    "pn_edgeconv_finalize_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                             c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "pn_edgeconv_bwd_prep_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                         c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "pn_edgeconv_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "pn_edgeconv_csr_build": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "pn_edgeconv_bwd_prebuilt": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 +
-                                 [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_edgeconv_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                    c_void_p, c_size_t, c_void_p]),
-    "pn_edgeconv_bwd_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                    c_void_p, c_size_t, c_void_p]),
-    "pn_dot_select_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "pn_dot_select_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_meanshift_slices": (c_int, [c_int, c_int]),
-    "pn_meanshift_pack_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_iter_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_meanshift_x3_image_bytes": (c_size_t, [c_int, c_int]),
-    "pn_meanshift_x3_split_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_x3_iter_fwd_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
-    "pn_meanshift_x3_iter_bwd_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 8 + [c_void_p]),
-    "pn_meanshift_w_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pn_meanshift_w_iter_fwd_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 4 +
-                                    [c_size_t, c_int, c_void_p]),
-    "pn_meanshift_w_iter_bwd_f32": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int] + [c_void_p] * 3 +
-                                    [c_size_t, c_int, c_void_p]),
-    "pn_meanshift_w_iter_fwd_kind_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 4 +
-                                         [c_size_t, c_int, c_int, c_void_p]),
-    "pn_meanshift_w_iter_bwd_kind_f32": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int] + [c_void_p] * 3 +
-                                         [c_size_t, c_int, c_int, c_void_p]),
-    "pn_meanshift_x3_iter_fwd_kind_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 5 +
-                                          [c_void_p, c_int, c_void_p]),
-    "pn_meanshift_x3_iter_bwd_kind_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 8 +
-                                          [c_void_p, c_int, c_void_p]),
-    "pn_meanshift_x3_exec_tiles": (c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
-    "pn_meanshift_x3_nearest_f32": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_gemm_x3_weight_image_bytes": (c_size_t, [c_int, c_int]),
-    "pn_gemm_x3_points_image_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pn_gemm_x3_weight_image_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_gemm_x3_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
-                               c_void_p]),
-    "pn_standardize_select_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_standardize_scale_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
-                                         c_void_p]),
-    "pn_gather_flat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "pn_adam_flat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float,
-                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, c_int, c_void_p]),
-    "pn_gemm_x3_cat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                   c_size_t, c_void_p]),
-    "pn_gemm_x3_wgrad_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pn_gemm_x3_wgrad_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_size_t, c_void_p]),
-    "pn_meanshift_rows_bwd_workspace": (c_size_t, [c_int, c_int]),
-    "pn_meanshift_rows_bwd_f32": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_size_t, c_void_p]),
-    "pn_meanshift_rows_scatter_add_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_x3_plan_bytes": (c_size_t, [c_int, c_int]),
-    "pn_meanshift_x3_plan_core_bytes": (c_size_t, [c_int, c_int]),
-    "pn_gn_max_finish_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 5),
-    "pn_gn_max_bwd_prep_f32": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 3),
-    "pn_cell_order_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_kmeans_assign_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_kmeans_centres_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_chain_order_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_x3_tileinfo_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_meanshift_x3_plan_f32": (c_int, [c_void_p] * 6 + [c_int, c_int, c_float, c_void_p, c_void_p]),
-    "pn_meanshift_x3_iter_fwd_plan_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 5 +
-                                          [c_void_p, c_void_p]),
-    "pn_meanshift_x3_iter_fwd_info_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 5 +
-                                          [c_void_p] * 5),
-    "pn_meanshift_x3_iter_bwd_plan_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 8 +
-                                          [c_void_p, c_void_p]),
-    "pn_dot_kth_x3_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                  c_void_p, c_size_t, c_void_p]),
-    "pn_dot_kth_unit_h2_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_size_t, c_void_p]),
-    "pn_meanshift_h2_image_bytes": (c_size_t, [c_int, c_int]),
-    "pn_meanshift_h2_split_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_meanshift_h2_iter_fwd_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
-    "pn_meanshift_h2_iter_bwd_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 8 + [c_void_p]),
-    "pn_meanshift_iter_bwd_f32": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 9 + [c_void_p]),
-    "pn_gn_rows_fwd_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "pn_gn_group_moments_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                        c_void_p, c_void_p]),
-    "pn_gn_apply_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                    c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "pn_gn_rows_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                   c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "pn_gn_group_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                    c_void_p]),
-    "pn_gn_apply_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_void_p]),
-    "pn_sym3_eig_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "pn_chamfer_nn_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "pn_chamfer_nn_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_chamfer_nn_ragged_workspace": (c_size_t, [c_int, c_int]),
-    "pn_chamfer_nn_ragged_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_chamfer_ragged_reduce_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "pn_coverage_reduce_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "pn_chamfer_ragged_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_int, c_void_p, c_void_p]),
-    "pn_gather_rows3_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pn_weighted_moments_chunks": (c_int, []),
-    "pn_weighted_moments_count": (c_int, []),
-    "pn_weighted_moments_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "pn_primitive_fit_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_cone_angle_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_primitive_residual_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_weighted_moments_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_bspline_eval_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_void_p, c_void_p]),
-    "pn_bspline_eval_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_void_p, c_void_p]),
-    "pn_edgeconv_bwd_stats_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "pn_edgeconv_bwd_stats_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float] + [c_void_p] * 5 +
-                                  [c_size_t, c_void_p]),
-    "pn_triplet_fwd_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
-                                   c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_triplet_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "pn_triplet_bwd_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                   c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pn_membership_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float] + [c_void_p] * 5 + [c_void_p]),
-    "pn_membership_bwd_f32": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 2 + [c_void_p]),
-    "pn_nms_occupied_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pn_nms_vote_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3 + [c_void_p]),
-    "pn_weighted_max_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float] + [c_void_p] * 3 + [c_void_p]),
-    "pn_weighted_max_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "pn_affine_act_fwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p]),
-    "pn_affine_act_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p]),
-    "pn_lsa_auction_f64": (c_int, [c_void_p] * 4 + [c_int, c_double, c_double, c_double, c_int, c_int] +
-                           [c_void_p] * 5 + [c_void_p]),
-    "pn_grid_occupancy_tile": (c_int, []),
-    "pn_grid_occupancy_ragged_f32": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p]),
-    "pn_trimesh_area_f64": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
-    "pn_trimesh_sample_f64": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "pn_point_primitive_min_tile": (c_int, []),
-    "pn_point_primitive_min_f32": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
-}
+def _ctype(text, decl, returned=False):
+    """The ctypes class of one C type as the header writes it.  Scalars by value; a pointer of any depth is
+    c_void_p (call sites pass ``tensor.data_ptr()`` ints, which a typed POINTER would reject), except the two
+    string forms: a returned ``const char*`` and a ``char*`` parameter.  Anything else raises: no default."""
+    words = text.replace("*", " * ").split()
+    base = " ".join(w for w in words if w not in ("*", "const"))
+    if "(" in text or ")" in text or not base:
+        raise ValueError("parsenet_hip.h: cannot bind `%s`: unsupported type `%s`" % (decl, text.strip()))
+    if "*" in words:
+        string = words == (["const", "char", "*"] if returned else ["char", "*"])
+        return ctypes.c_char_p if string else ctypes.c_void_p
+    if returned and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise ValueError("parsenet_hip.h: cannot bind `%s`: no ctypes scalar for `%s`" % (decl, base))
+    return _SCALARS[base]
+
+
+def parse_header(text):
+    """({name: (restype, argtypes)}, {PN_* integer #define: value}) of the text of a C header that holds
+    nothing but comments, preprocessor lines and function declarations with named parameters."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text.replace("\\\n", " "), flags=re.S)
+    constants = {name: int(value) for name, value in _CONSTANT.findall(text)}
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)
+    signatures = {}
+    for decl in text.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = _DECLARATION.fullmatch(decl)
+        if m is None:
+            raise ValueError("parsenet_hip.h: cannot parse the declaration `%s`" % decl)
+        restype, name, params = m.groups()
+        argtypes = []
+        if params.strip() != "void":
+            for param in params.split(","):
+                named = re.fullmatch(r"(.*[\s*])\w+\s*", param, re.S)      # the type, then the parameter's name
+                if named is None:
+                    raise ValueError("parsenet_hip.h: cannot bind `%s`: parameter `%s`" % (decl, param.strip()))
+                argtypes.append(_ctype(named.group(1), decl))
+        signatures[name] = (_ctype(restype, decl, returned=True), argtypes)
+    return signatures, constants
+
+
+# name -> (restype, argtypes) and the PN_* constants, read once from the header: the one place the C ABI is written
+with open(HEADER_PATH) as _f:
+    SIGNATURES, CONSTANTS = parse_header(_f.read())
+ABI_VERSION = CONSTANTS["PN_ABI_VERSION"]  # pn_abi_version() of the library these signatures describe
 
 _lib = None
 
@@ -467,7 +339,7 @@ def prof_results():
     out = {}
     buf = ctypes.create_string_buffer(128)
     for i in range(lib.pn_prof_count()):
-        ms = c_double()
+        ms = ctypes.c_double()
         calls = ctypes.c_longlong()
         if lib.pn_prof_get(i, buf, 128, ctypes.byref(ms), ctypes.byref(calls)) == 0:
             out[buf.value.decode()] = (ms.value, calls.value)

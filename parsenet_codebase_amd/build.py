@@ -12,6 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")   # parsenet_hip.h: csrc/common.h includes it
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libparsenet_hip.so")
 
@@ -28,6 +29,7 @@ FLAGS = os.environ.get("PN_EXTRA_HIPCC_FLAGS", "").split() + [
     "-fno-fast-math",
     "-Wall",
     "-Wno-unused-function",
+    "-I" + INCLUDE,
 ]
 
 
@@ -37,10 +39,10 @@ def _sources():
 
 def _digest(path):
     h = hashlib.sha1()
-    for name in sorted(os.listdir(CSRC)):
-        if name.endswith(".h"):
-            with open(os.path.join(CSRC, name), "rb") as f:
-                h.update(f.read())
+    headers = [os.path.join(CSRC, name) for name in sorted(os.listdir(CSRC)) if name.endswith(".h")]
+    for name in headers + [os.path.join(INCLUDE, "parsenet_hip.h")]:
+        with open(name, "rb") as f:
+            h.update(f.read())
     with open(path, "rb") as f:
         h.update(f.read())
     h.update(" ".join(FLAGS).encode())

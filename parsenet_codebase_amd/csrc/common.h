@@ -9,15 +9,12 @@
 
 #define PN_WAVE 64
 
-// ---- error reporting (thread-local, see include/parsenet_hip.h) ------------
-extern "C" const char* pn_last_error(void);
-void pn_set_error(const char* fmt, ...);
+// The public C ABI: every extern "C" definition in csrc/ is compiled against its declaration there
+// (a mismatch is a conflicting-types error), and PN_OK / PN_ERR_* / PN_ABI_VERSION come from it.
+#include "parsenet_hip.h"
 
-#define PN_OK 0
-#define PN_ERR_ARG (-1)
-#define PN_ERR_HIP (-2)
-#define PN_ERR_WORKSPACE (-3)
-#define PN_ERR_UNSUPPORTED (-4)
+// ---- error reporting (thread-local, see include/parsenet_hip.h) ------------
+void pn_set_error(const char* fmt, ...);
 
 #define PN_CHECK_ARG(cond, ...)                 \
   do {                                          \

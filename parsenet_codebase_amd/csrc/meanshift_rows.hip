@@ -383,7 +383,8 @@ static int mr_rows_bwd(const float* gy, const float* y, const float* q, const fl
 extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum,
                                          const float* unorm, const float* x, const float* bsq, int B, int N, int D,
                                          int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
-                                         hipStream_t stream) {
+                                         void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   PN_CHECK_ARG(D == 32 || D == 64 || D == 128, "pn_meanshift_rows_bwd_f32: D must be one of {32, 64, 128}, got %d", D);
   PN_CHECK_ARG(R >= 1 && R <= MR_R, "pn_meanshift_rows_bwd_f32: 1 <= R <= %d, got %d", MR_R, R);
   PN_CHECK_ARG(B >= 1 && N >= 1, "pn_meanshift_rows_bwd_f32: empty input");
@@ -397,7 +398,8 @@ extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const 
 }
 
 extern "C" int pn_meanshift_rows_scatter_add_f32(const float* g, const int64_t* rows, int B, int N, int D, int R,
-                                                 float* gx, hipStream_t stream) {
+                                                 float* gx, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   PN_CHECK_ARG(D == 32 || D == 64 || D == 128, "pn_meanshift_rows_scatter_add_f32: D must be one of {32, 64, 128}, got %d",
                D);
   PN_CHECK_ARG(B >= 1 && R >= 1, "pn_meanshift_rows_scatter_add_f32: empty input");

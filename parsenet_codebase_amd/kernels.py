@@ -333,7 +333,7 @@ def dot_kth_x3(q, c, k):
     with _lib.on_device(dev):
         rc = lib.pn_dot_kth_x3_f32(ptr(q), Nq, ptr(c), Nc, B, C, int(k), ptr(out), ptr(flags), ptr(ws), wsz,
                                    current_stream(dev))
-    if rc == -4:      # PN_ERR_UNSUPPORTED: shape outside the split passes
+    if rc == _lib.CONSTANTS["PN_ERR_UNSUPPORTED"]:      # shape outside the split passes
         return None
     check(rc, "pn_dot_kth_x3_f32")
     return out, flags
@@ -570,7 +570,8 @@ def meanshift_x3_plan_visited(plans, B, N):
     return torch.stack([p[:n].sum(dtype=torch.float32) for p in plans]).mean() / float(n)
 
 
-KERNEL_GAUSSIAN, KERNEL_EPANECHNIKOV = 0, 1      # PN_MS_KERNEL_* of include/parsenet_hip.h
+KERNEL_GAUSSIAN = _lib.CONSTANTS["PN_MS_KERNEL_GAUSSIAN"]
+KERNEL_EPANECHNIKOV = _lib.CONSTANTS["PN_MS_KERNEL_EPANECHNIKOV"]
 
 
 def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=False, kind=KERNEL_GAUSSIAN):
