@@ -773,6 +773,37 @@ int pn_point_primitive_min_f32(const float* points, const int* pt_off, const int
                                const float* prim_par, const float* samp, const int* samp_off, const int* tile_shape,
                                const int* tile_first, int B, int total_tiles, float* dmin, int* arg, void* stream);
 
+/* ---- exact distance from points to the trimmed surfaces (csrc/tridist.hip, arithmetic: csrc/tri_math.h) --------
+ * The distance from every point of a shape to the nearest triangle of the kept cells of the shape's surfaces: the
+ * limit, for infinitely many samples, of the distance to the nearest sample that the coverage metrics use.
+ * Two launches for a ragged batch of B shapes.  The mesh tables are those of pn_trimesh_area_f64 over the M meshes
+ * of all shapes, a shape's meshes consecutive: shape b owns the faces shape_face[b] .. shape_face[b+1]
+ * (shape_face (B+1) = face_off at the shape's first mesh) and the triangle SLOTS slot_off[b] .. slot_off[b+1]
+ * (slot_off (B+1), slot_off[0] = 0, a shape's slot count = its face count rounded up to a multiple of
+ * pn_trimesh_group(), at least one face per shape); total_slots = slot_off[B].
+ *   records: rec (16 * total_slots) fp32, structure of arrays: rec[k * total_slots + slot] = value k of the slot's
+ *   triangle (vertex opposite the longest edge, two edges, their cross product, four reciprocals; padding slots hold
+ *   a record no finite point is nearest to); sph (total_slots / group, 4) fp32, 16-byte aligned: centre and radius
+ *   of a ball that holds the group's triangles.
+ *   distance: points (T,3) fp32, shape b rows pt_off[b] .. pt_off[b+1]; a workgroup of `waves` (4, 8 or 16) waves
+ *   owns pn_trimesh_point_dist_tile() consecutive points of one shape: tile t starts at row tile_first[t] of shape
+ *   tile_shape[t]; total_tiles = sum_b ceil(N_b / tile).  dist2 (T) fp32: the squared distance to the nearest
+ *   triangle; face (T) int32: its index among the shape's faces, the lowest on equal distances.  prune != 0 skips
+ *   groups whose certified lower bound exceeds the running minimum of all 64 points of a wave; the results are the
+ *   same bits for prune 0 and 1, for every `waves`, and from run to run.  skipped (one 64-bit counter, optional):
+ *   the number of groups skipped is ADDED to it.
+ * All tables are DEVICE arrays of int32.  Limits: int32 offsets (3 T, 16 total_slots < 2^31); coordinates far
+ * below 1e18 in magnitude. */
+int pn_trimesh_group(void);
+int pn_trimesh_point_dist_tile(void);
+int pn_trimesh_records_f32(const float* grid, const int* voff, const int* size_v, const int* face_off,
+                           const int* cells, int M, const int* shape_face, const int* slot_off, int B,
+                           int total_slots, float* rec, float* sph, void* stream);
+int pn_trimesh_point_dist_f32(const float* points, const int* pt_off, const int* slot_off, const float* rec,
+                              int total_slots, const float* sph, const int* tile_shape, const int* tile_first, int B,
+                              int total_tiles, int waves, int prune, float* dist2, int* face,
+                              unsigned long long* skipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

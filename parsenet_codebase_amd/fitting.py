@@ -1045,13 +1045,15 @@ class Evaluation:
                                    quantile, iterations, lamb, if_optimize)
 
     def reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw=0.01,
-                          if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000):
+                          if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000,
+                          surface_distance=False):
         """test.py:108-185 for B shapes from given cluster ids: parameters, trimmed surfaces, samples and the table of
         seg-IoU, type-IoU, s-cover, p-cover and CD per shape, stage by stage (fitting_eval.reconstruct_batch).  The
-        trimmed surfaces of the LS refit (``if_optimize=True``) are available here only."""
+        trimmed surfaces of the LS refit (``if_optimize=True``) are available here only.  ``surface_distance`` adds
+        the coverage against the surfaces themselves (p_cover_surface, p_dist_surface)."""
         from .fitting_eval import reconstruct_batch
         return reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw,
-                                 if_optimize, if_visualize, epsilon, n_samples)
+                                 if_optimize, if_visualize, epsilon, n_samples, surface_distance)
 
     def fitting_losses_pipelined(self, embedding, points, normals, labels, primitives, primitives_log_prob,
                                  quantile=0.125, iterations=5, lamb=1.0, chunks=2):

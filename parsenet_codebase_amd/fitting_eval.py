@@ -804,7 +804,7 @@ def _device_rows(rows, whole, given, dev):
 
 
 def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw=0.01,
-                      if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000):
+                      if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000, surface_distance=False):
     """What test.py:108-185 computes for one shape — residual_eval_mode(sample_points=True), the trimmed surfaces,
     sample_from_collection_of_mesh, the coverage figures and the IoUs — for B shapes, stage by stage: the fitting
     stage of this module from the GIVEN cluster ids (no embedding, no mean-shift), the analytic grids on the host in
@@ -820,10 +820,13 @@ def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred
     Returns one dict per shape: parameters (as residual_eval_mode), surfaces ([TrimmedSurface]), samples ((M_b,3) fp32
     on the device), metrics (sk_1, sk_2, sk, pk_1, pk_2, pk, cd, s_iou, p_iou) — or metrics None, samples None and
     ``message`` when the sampling of that shape fails (no surface with a kept cell, or none that gets more than 10
-    points), as test.py:152-156 skips such a shape.  Argument errors raise ValueError with the shape index."""
+    points), as test.py:152-156 skips such a shape.  Argument errors raise ValueError with the shape index.
+    ``surface_distance``: the metrics also carry p_cover_surface and p_dist_surface, sk_1 and sk taken against the
+    trimmed surfaces themselves instead of their samples (metrics.surface_coverage_batch: two more launches and one
+    more download for the batch; no random draw, nothing else changes)."""
     from . import surface
     from .fitting import SIOU_matched_segments, to_one_hot, up_sample_points_torch_memory_efficient
-    from .metrics import coverage_rows
+    from .metrics import coverage_rows, surface_coverage_batch
     pts_l, nrm_l, lab_l, cid_l, prim_l, pp_l, seeds, whole = _reconstruct_args(
         points, normals, labels, cluster_ids, primitives, pred_primitives, seeds)
     B = len(pts_l)
@@ -975,6 +978,10 @@ def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred
         live = [b for b in range(B) if samples[b] is not None]
         rows = coverage_rows([samples[b] for b in live], [P[b, :counts_n[b]] for b in live]) if live else []
         downloads += 1 if live else 0
+        exact = []
+        if surface_distance and live:
+            exact = surface_coverage_batch([P[b, :counts_n[b]] for b in live], [surfaces[b] for b in live])
+            downloads += 1
         records = []
         for b in range(B):
             rec = {"parameters": st["parameters"][b], "surfaces": surfaces[b], "samples": samples[b], "metrics": None,
@@ -983,6 +990,8 @@ def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred
                 m = rows[live.index(b)]
                 weights = to_one_hot(cid_l[b], np.unique(cid_l[b]).shape[0], device_id=dev.index)
                 m["s_iou"], m["p_iou"], _, _ = SIOU_matched_segments(lab_l[b], cid_l[b], pp_l[b], prim_l[b], weights)
+                if exact:
+                    m.update(exact[live.index(b)])
                 rec["metrics"] = m
             records.append(rec)
     CALLS_RECONSTRUCT["shapes"] += B

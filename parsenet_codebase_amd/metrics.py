@@ -84,6 +84,27 @@ def coverage_metrics_batch(pred_points_list, points_list):
     return [{k: float(v) for k, v in r.items()} for r in coverage_rows(both[0], both[1])]
 
 
+def surface_coverage_batch(points_list, surfaces_list):
+    """The deterministic limit of the s-coverage figures ``coverage_metrics`` forms from the nearest SAMPLE of the
+    reconstruction (sk_1: the share of input points within 0.01 of it, sk: their mean distance): the same figures
+    from the distance to the nearest TRIANGLE of the trimmed surfaces (surface.point_surface_distance, one record
+    and one distance launch for the batch).  Per shape {"p_cover_surface", "p_dist_surface"}: guard_sqrt of the
+    squared distance, the share of roots < 0.01 and the mean root, both formed in float64.  One download."""
+    from . import surface
+    from .fitting import guard_sqrt
+    rows = []
+    for d2 in surface.point_surface_distance(points_list, surfaces_list):
+        root = guard_sqrt(d2)
+        rows.append(torch.stack([(root < 0.01).double().mean(), root.double().mean()]))
+    table = torch.stack(rows).cpu().numpy()
+    return [{"p_cover_surface": float(r[0]), "p_dist_surface": float(r[1])} for r in table]
+
+
+def surface_coverage(points, surfaces):
+    """``surface_coverage_batch`` of one shape."""
+    return surface_coverage_batch([points], [surfaces])[0]
+
+
 # ---------------------------------------------------------------------------------------
 # src/segment_utils.py: the remaining segmentation metrics and membership helpers
 # ---------------------------------------------------------------------------------------

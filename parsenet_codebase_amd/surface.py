@@ -368,3 +368,125 @@ def sample_from_collection_of_mesh(Meshes, N=10000, return_faces=False):
         f = face.cpu().numpy()
         return points, [f[samp_off[i]:samp_off[i + 1]] for i in range(len(take))]
     return points
+
+
+# ---------------------------------------------------------------------------------------
+# exact distance from points to the trimmed surfaces (csrc/tridist.hip)
+# ---------------------------------------------------------------------------------------
+# launches of point_surface_distance (one of each per call, whatever the batch)
+CALLS_TRIDIST = {"records": 0, "distance": 0}
+# the last pruned call: "skipped" a one-element int64 tensor on the device (groups of triangles the waves skipped;
+# reading it synchronises), "visits" the number of (wave, group) pairs an unpruned call walks
+LAST_PRUNE = {"skipped": None, "visits": 0}
+
+
+def _tridist_args(points_list, surfaces_list):
+    """Host-only argument checks of point_surface_distance -> per shape the positions of the surfaces with a kept
+    cell.  ValueError names the shape."""
+    if len(points_list) != len(surfaces_list) or len(points_list) < 1:
+        raise ValueError("point_surface_distance: %d point clouds for %d lists of surfaces"
+                         % (len(points_list), len(surfaces_list)))
+    kept = []
+    for b, (p, surfaces) in enumerate(zip(points_list, surfaces_list)):
+        shape = tuple(p.shape) if hasattr(p, "shape") else np.asarray(p).shape
+        if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+            raise ValueError("point_surface_distance: shape %d: points must be (N,3) with N >= 1, got %s"
+                             % (b, tuple(shape)))
+        pos = [i for i, s in enumerate(surfaces) if s.mask.any()]
+        if not pos:
+            raise ValueError("point_surface_distance: shape %d has no kept triangle (%d surfaces, none with a kept "
+                             "cell)" % (b, len(surfaces)))
+        kept.append(pos)
+    return kept
+
+
+def _morton_order(points, shape_of_row):
+    """Rows ordered shape by shape and, inside a shape, along a 30-bit Morton curve through the batch's bounding box:
+    the 64 points of a wave are then neighbours, which is what lets a wave skip a group of triangles.  The order has
+    no influence on any result (a point's result depends on the point alone)."""
+    lo = points.min(0).values
+    span = (points.max(0).values - lo).clamp_min(1e-30)
+    q = ((points - lo) / span * 1023.0).to(torch.int64).clamp_(0, 1023)
+    q = (q | (q << 16)) & 0x30000FF
+    q = (q | (q << 8)) & 0x300F00F
+    q = (q | (q << 4)) & 0x30C30C3
+    q = (q | (q << 2)) & 0x9249249
+    code = q[:, 0] | (q[:, 1] << 1) | (q[:, 2] << 2) | (shape_of_row << 30)
+    return torch.argsort(code)
+
+
+def point_surface_distance(points_list, surfaces_list, prune=True, return_index=False, waves=None):
+    """Per shape the (N_b,) float32 SQUARED distance from every point to the nearest triangle of the kept cells of
+    the shape's trimmed surfaces — the surface itself, not samples of it.  points_list[b]: (N_b,3) array or tensor;
+    surfaces_list[b]: a list of TrimmedSurface (those without a kept cell are skipped; a shape left with none raises
+    ValueError naming it).  ``return_index``: per shape (d2, surface, face) with the position of the nearest surface
+    in surfaces_list[b] and the face id within it (TrimmedSurface.triangles() order), int64, the lowest on equal
+    distances.  ``prune`` skips groups of triangles by a certified bound; results are bit-identical with it on and
+    off.  ``waves`` (4, 8, 16; default by the number of point tiles) is the workgroup size of the distance pass and
+    has no influence on the results either.  ONE record launch and ONE distance launch for the whole batch."""
+    kept = _tridist_args(points_list, surfaces_list)
+    B = len(kept)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pts = [torch.from_numpy(np.asarray(p, np.float32)).to(dev) if not torch.is_tensor(p)
+           else p.detach().to(device=dev, dtype=torch.float32) for p in points_list]
+    flat = [surfaces_list[b][i] for b in range(B) for i in kept[b]]
+    grid, voff, sv, foff, cells, face_off = _mesh_tables(flat, dev)
+    lib = _lib.load()
+    group, tile = lib.pn_trimesh_group(), lib.pn_trimesh_point_dist_tile()
+    mesh_off = np.concatenate([[0], np.cumsum([len(k) for k in kept])])
+    shape_face = face_off[mesh_off]
+    slots = (np.diff(shape_face) + group - 1) // group * group
+    slot_off = np.concatenate([[0], np.cumsum(slots)])
+    counts = np.asarray([p.shape[0] for p in pts], np.int64)
+    pt_off = np.concatenate([[0], np.cumsum(counts)])
+    total_slots, T = int(slot_off[-1]), int(pt_off[-1])
+    if max(3 * T, 16 * total_slots, 3 * grid.shape[0]) >= 2 ** 31:
+        raise ValueError("point_surface_distance: int32 offsets")
+    ntile = (counts + tile - 1) // tile
+    tile_shape = np.repeat(np.arange(B), ntile)
+    tile_first = np.concatenate([pt_off[b] + tile * np.arange(ntile[b]) for b in range(B)])
+    total_tiles = int(ntile.sum())
+    if waves is None:
+        waves = 16 if total_tiles <= 256 else 8 if total_tiles <= 512 else 4
+    table = h2d(np.concatenate([shape_face, slot_off, pt_off, tile_shape, tile_first]).astype(np.int32), dev)
+    o = np.cumsum([0, B + 1, B + 1, B + 1, total_tiles])
+    c_face, c_slot, c_pt, c_tshape, c_tfirst = [table[o[i]:o[i + 1] if i + 1 < len(o) else None]
+                                                 for i in range(len(o))]
+    rec = torch.empty(16 * total_slots, dtype=torch.float32, device=dev)
+    sph = torch.empty(total_slots // group, 4, dtype=torch.float32, device=dev)
+    allp = (pts[0] if B == 1 else torch.cat(pts)).contiguous()
+    order = None
+    if prune:
+        order = _morton_order(allp, h2d(np.repeat(np.arange(B), counts), dev))
+        allp = allp[order].contiguous()
+    d2 = torch.empty(T, dtype=torch.float32, device=dev)
+    face = torch.empty(T, dtype=torch.int32, device=dev)
+    skipped = torch.zeros(1, dtype=torch.int64, device=dev) if prune else None
+    with _lib.on_device(dev):
+        stream = current_stream(dev)
+        rc = lib.pn_trimesh_records_f32(ptr(grid), ptr(voff), ptr(sv), ptr(foff), ptr(cells), len(flat), ptr(c_face),
+                                        ptr(c_slot), B, total_slots, ptr(rec), ptr(sph), stream)
+        check(rc, "pn_trimesh_records_f32")
+        CALLS_TRIDIST["records"] += 1
+        rc = lib.pn_trimesh_point_dist_f32(ptr(allp), ptr(c_pt), ptr(c_slot), ptr(rec), total_slots, ptr(sph),
+                                           ptr(c_tshape), ptr(c_tfirst), B, total_tiles, int(waves),
+                                           1 if prune else 0, ptr(d2), ptr(face), ptr(skipped), stream)
+        check(rc, "pn_trimesh_point_dist_f32")
+        CALLS_TRIDIST["distance"] += 1
+    if prune:
+        LAST_PRUNE["skipped"] = skipped
+        LAST_PRUNE["visits"] = int((ntile * (slots // group)).sum())
+        d2 = torch.empty_like(d2).index_copy_(0, order, d2)
+        face = torch.empty_like(face).index_copy_(0, order, face)
+    out = []
+    for b in range(B):
+        # own storage per shape: what a caller reduces must not depend on the batch the shape was evaluated in
+        d = d2[pt_off[b]:pt_off[b + 1]].clone()
+        if not return_index:
+            out.append(d)
+            continue
+        f = face[pt_off[b]:pt_off[b + 1]].long()
+        local = face_off[mesh_off[b]:mesh_off[b + 1] + 1] - face_off[mesh_off[b]]
+        m = torch.searchsorted(h2d(local[1:].astype(np.int64), dev), f, right=True)
+        out.append((d, h2d(np.asarray(kept[b], np.int64), dev)[m], f - h2d(local.astype(np.int64), dev)[m]))
+    return out
