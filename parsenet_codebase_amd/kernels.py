@@ -373,6 +373,7 @@ class MeanShiftWorkspace:
         f = dict(dtype=torch.float32, device=device)
         self.opart = torch.empty((B, self.S, N, D), **f)
         self.rpart = torch.empty((B, self.S, N), **f)
+        self.x3_imgs = self.h2_imgs = None      # tile images of the split backwards, made by their first step
         if backward:
             self.gu = torch.empty((B, N, D), **f)
             # row scalars (+ the per-tile maxima of the fp16 path)
@@ -574,6 +575,20 @@ KERNEL_GAUSSIAN = _lib.CONSTANTS["PN_MS_KERNEL_GAUSSIAN"]
 KERNEL_EPANECHNIKOV = _lib.CONSTANTS["PN_MS_KERNEL_EPANECHNIKOV"]
 
 
+def _ms_out(who, q, out):
+    """The (y (B,N,D), rsum (B,N), unorm (B,N)) triple a forward step on q (B,N,D) writes: ``out`` checked, or
+    allocated when it is None."""
+    B, N, D = q.shape
+    if out is None:
+        return (torch.empty_like(q), torch.empty((B, N), dtype=torch.float32, device=q.device),
+                torch.empty((B, N), dtype=torch.float32, device=q.device))
+    for t, shp in zip(out, ((B, N, D), (B, N), (B, N))):
+        if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != q.device:
+            raise ValueError("%s: out tensors must be contiguous fp32 of shapes (B,N,D), (B,N), (B,N)" % who)
+    y, rsum, unorm = out
+    return y, rsum, unorm
+
+
 def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=False, kind=KERNEL_GAUSSIAN):
     """``out`` = (y (B,N,D), rsum (B,N), unorm (B,N)) contiguous fp32 tensors to write into (slices of
     the buffers that keep all iterates of a call together), or None: allocated here.  ``want_info``: also
@@ -583,15 +598,7 @@ def meanshift_x3_iter_fwd(q, x_image, bsq, ws, plan=None, out=None, want_info=Fa
     B, N, D = q.shape
     if kind != KERNEL_GAUSSIAN and want_info:
         raise ValueError("meanshift_x3_iter_fwd: the caps of the iterate feed the plans, which are Gaussian-only")
-    if out is not None:
-        y, rsum, unorm = out
-        for t, shp in ((y, (B, N, D)), (rsum, (B, N)), (unorm, (B, N))):
-            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != q.device:
-                raise ValueError("meanshift_x3_iter_fwd: out tensors must be contiguous fp32 of shapes (B,N,D), (B,N), (B,N)")
-    else:
-        y = torch.empty_like(q)
-        rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
-        unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    y, rsum, unorm = _ms_out("meanshift_x3_iter_fwd", q, out)
     if not want_info:
         with _lib.on_device(q.device):
             rc = _lib.load().pn_meanshift_x3_iter_fwd_kind_f32(ptr(q), ptr(x_image), ptr(bsq), B, N, D, ptr(ws.opart),
@@ -619,7 +626,7 @@ def meanshift_x3_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx, plan=N
     gy = _f32c(gy, "gy")
     gq = torch.empty_like(x)
     lib = _lib.load()
-    if getattr(ws, "x3_imgs", None) is None:
+    if ws.x3_imgs is None:
         nbytes = lib.pn_meanshift_x3_image_bytes(B, N)
         ws.x3_imgs = [torch.empty(nbytes, dtype=torch.uint8, device=x.device) for _ in range(2)]
     im = ws.x3_imgs
@@ -683,15 +690,7 @@ def meanshift_w_iter_fwd(q, x, bsq, ws, out=None, kind=KERNEL_GAUSSIAN):
     bsq = _msw_bsq(bsq, B, x.device)
     if tuple(q.shape) != (B, N, D) or (ws.B, ws.N, ws.D, ws.backward) != (B, N, D, False):
         raise ValueError("meanshift_w_iter_fwd: q, x (B,N,D) and a forward workspace of that shape")
-    if out is not None:
-        y, rsum, unorm = out
-        for t, shp in ((y, (B, N, D)), (rsum, (B, N)), (unorm, (B, N))):
-            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != q.device:
-                raise ValueError("meanshift_w_iter_fwd: out tensors must be contiguous fp32 of shapes (B,N,D), (B,N), (B,N)")
-    else:
-        y = torch.empty_like(q)
-        rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
-        unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    y, rsum, unorm = _ms_out("meanshift_w_iter_fwd", q, out)
     with _lib.on_device(q.device):
         rc = _lib.load().pn_meanshift_w_iter_fwd_kind_f32(ptr(q), ptr(x), ptr(bsq), B, N, D, ptr(y), ptr(rsum),
                                                           ptr(unorm), ptr(ws.buf), ws.buf.numel(),
@@ -910,9 +909,7 @@ def meanshift_h2_split(x):
 
 def meanshift_h2_iter_fwd(q, x_image, bsq, ws):
     B, N, D = q.shape
-    y = torch.empty_like(q)
-    rsum = torch.empty((B, N), dtype=torch.float32, device=q.device)
-    unorm = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    y, rsum, unorm = _ms_out("meanshift_h2_iter_fwd", q, None)
     with _lib.on_device(q.device):
         rc = _lib.load().pn_meanshift_h2_iter_fwd_f32(ptr(q), ptr(x_image), ptr(bsq), B, N, D, ptr(ws.opart),
                                                       ptr(ws.rpart), ptr(y), ptr(rsum), ptr(unorm),
@@ -927,7 +924,7 @@ def meanshift_h2_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx):
     gy = _f32c(gy, "gy")
     gq = torch.empty_like(x)
     lib = _lib.load()
-    if getattr(ws, "h2_imgs", None) is None:
+    if ws.h2_imgs is None:
         nbytes = lib.pn_meanshift_h2_image_bytes(B, N)
         ws.h2_imgs = [torch.empty(nbytes, dtype=torch.uint8, device=x.device) for _ in range(2)]
     im = ws.h2_imgs
@@ -942,9 +939,7 @@ def meanshift_h2_iter_bwd(gy, y, q, x, x_image, rsum, unorm, bsq, ws, gx):
 
 def meanshift_iter_fwd(q, x, xt, bsq, ws):
     B, N, D = x.shape
-    y = torch.empty_like(x)
-    rsum = torch.empty((B, N), dtype=torch.float32, device=x.device)
-    unorm = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    y, rsum, unorm = _ms_out("meanshift_iter_fwd", x, None)
     with _lib.on_device(x.device):
         rc = _lib.load().pn_meanshift_iter_fwd_f32(ptr(q), ptr(x), ptr(xt), ptr(bsq), B, N, D, ptr(ws.opart),
                                                    ptr(ws.rpart), ptr(y), ptr(rsum), ptr(unorm),

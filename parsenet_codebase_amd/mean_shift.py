@@ -3,6 +3,7 @@ kernels: bandwidth quantile and nearest-centre assignment through the matrix-cor
 engine, iterations through the fused flash-style kernels with a recompute backward.  Same class,
 method names and return values as the reference."""
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -202,42 +203,117 @@ def locality_order(x, lloyd=2):
     return torch.argsort(key, dim=1, stable=True)
 
 
-_SPLIT = {"fp16x2": (K.meanshift_h2_split, K.meanshift_h2_iter_fwd, K.meanshift_h2_iter_bwd),
-          "bf16x3": (K.meanshift_x3_split, K.meanshift_x3_iter_fwd, K.meanshift_x3_iter_bwd)}
+class _Route(NamedTuple):
+    """What one kernel family gives the driver of the iterations (``_run_iterations``) and the backward loop of
+    ``_MeanShiftIterations``.  One instance per family, chosen by ``_route``; a further family is a further
+    instance and a line in ``_route``."""
+    name: str
+    # x (B,N,D) -> the copy of the data the kernels stream, made once per call (tile images of 16-bit pieces,
+    # channel-first fp32); None: the kernels read x itself
+    operand: object
+    # (B, N, D, device, backward) -> the scratch buffers the steps of a call share
+    workspace: object
+    # (q, x, operand, bsq, ws, plan, out, want_info, kind) -> (y, rsum, unorm[, info]): one step
+    fwd: object
+    # (gy, y, q, x, operand, rsum, unorm, bsq, ws, gx, plan, kind) -> dL/dq; adds the step's dL/dx into gx
+    bwd: object
+    plannable: bool     # its Gaussian launches take a block-sparse plan and return the caps of the iterate
+    writes_out: bool    # fwd writes into the ``out`` triple (the others' results are stacked afterwards)
+    kinds: tuple        # the kernel profiles it has kernels for
 
 
-def _run_iterations(X, bsq, iterations, stacked=False, rel_eps=None):
-    """The forward pass of the iterations (no autograd; ``rel_eps``: the bound of the plans, default
-    PLAN_REL_EPS).  Returns a dict: the operands in the order the
-    kernels ran on (``x``: the data, locality-ordered when the launches are planned; ``perm`` / ``inv``),
-    the iterates / row sums / norms of every step and the plans.  ``stacked``: the iterates, row sums and
-    norms of all steps live in ONE buffer each (``iterates_all`` (T+1,B,N,D), ``rsums_all`` / ``norms_all``
-    (T,B,N)) — what the row-restricted backward gathers its rows from in three launches."""
+_BOTH_KINDS = (K.KERNEL_GAUSSIAN, K.KERNEL_EPANECHNIKOV)
+_X3 = _Route(
+    "x3", K.meanshift_x3_split,
+    lambda B, N, D, dev, backward: K.MeanShiftWorkspace(B, N, D, dev, backward=backward, exact_f32=False),
+    lambda q, x, im, bsq, ws, plan, out, want_info, kind:
+        K.meanshift_x3_iter_fwd(q, im, bsq, ws, plan, out=out, want_info=want_info, kind=kind),
+    lambda gy, y, q, x, im, rsum, unorm, bsq, ws, gx, plan, kind:
+        K.meanshift_x3_iter_bwd(gy, y, q, x, im, rsum, unorm, bsq, ws, gx, plan, kind=kind),
+    plannable=True, writes_out=True, kinds=_BOTH_KINDS)
+_W = _Route(
+    "w", None,
+    lambda B, N, D, dev, backward: K.MeanShiftWWorkspace(B, N, D, dev, backward=backward),
+    lambda q, x, _, bsq, ws, plan, out, want_info, kind: K.meanshift_w_iter_fwd(q, x, bsq, ws, out=out, kind=kind),
+    lambda gy, y, q, x, _, rsum, unorm, bsq, ws, gx, plan, kind:
+        K.meanshift_w_iter_bwd(gy, y, q, x, rsum, unorm, bsq, ws, gx, kind=kind),
+    plannable=False, writes_out=True, kinds=_BOTH_KINDS)
+_H2 = _Route(
+    "h2", K.meanshift_h2_split,
+    _X3.workspace,
+    lambda q, x, im, bsq, ws, plan, out, want_info, kind: K.meanshift_h2_iter_fwd(q, im, bsq, ws),
+    lambda gy, y, q, x, im, rsum, unorm, bsq, ws, gx, plan, kind:
+        K.meanshift_h2_iter_bwd(gy, y, q, x, im, rsum, unorm, bsq, ws, gx),
+    plannable=False, writes_out=False, kinds=(K.KERNEL_GAUSSIAN,))
+_F32 = _Route(
+    "f32", K.meanshift_pack,
+    # (the exact backward also needs go and the channel-first copies of q and gu)
+    lambda B, N, D, dev, backward: K.MeanShiftWorkspace(B, N, D, dev, backward=backward, exact_f32=True),
+    lambda q, x, xt, bsq, ws, plan, out, want_info, kind: K.meanshift_iter_fwd(q, x, xt, bsq, ws),
+    lambda gy, y, q, x, xt, rsum, unorm, bsq, ws, gx, plan, kind:
+        K.meanshift_iter_bwd(gy, y, q, x, xt, rsum, unorm, bsq, ws, gx),
+    plannable=False, writes_out=False, kinds=(K.KERNEL_GAUSSIAN,))
+_ROUTES_128 = {"bf16x3": _X3, "fp16x2": _H2, "f32": _F32}
+
+
+def _route(D, kind):
+    """The kernel family that runs D-wide rows as they are with this kernel profile under ARITH and NARROW, or a
+    ValueError: widths that ``mean_shift_iterations`` pads first, and what has no kernel."""
+    wide = _ROUTES_128.get(ARITH)       # the arithmetic's route at 128; its kinds are the arithmetic's at any width
+    if kind != K.KERNEL_GAUSSIAN and (wide is None or kind not in wide.kinds):
+        raise ValueError("the fused Epanechnikov kernel is bf16x3 only, PARSENET_MS_ARITH is %r "
+                         "(MeanShift.mean_shift_ runs the tensor expressions then)" % ARITH)
+    if wide is None:
+        raise ValueError("PARSENET_MS_ARITH must be fp16x2, bf16x3 or f32, not %r" % ARITH)
+    if D == 128:
+        return wide
+    if kernel_width(D) == D:        # 32 and 64 under bf16x3 / native: the only narrow width kernels there are
+        return _W
+    raise ValueError("width %d does not run as it is with PARSENET_MS_NARROW=%s and PARSENET_MS_ARITH=%s; "
+                     "mean_shift_iterations zero-pads it to %s" % (D, NARROW, ARITH, kernel_width(D)))
+
+
+class _Iterations:
+    """What ``_run_iterations`` leaves behind: the route it took, the operands in the order the kernels ran on
+    (``x``: the data, locality-ordered when the launches were planned, ``perm`` / ``inv``; ``operand``: the route's
+    streamed copy of it), the final iterate ``q``, the iterates / row sums / norms of every step and the plans."""
+    __slots__ = ("route", "x", "operand", "sparse", "perm", "inv", "q", "iterates", "rsums", "norms", "plans",
+                 "iterates_all", "rsums_all", "norms_all")
+
+
+def _run_iterations(X, bsq, iterations, stacked=False, rel_eps=None, kind=K.KERNEL_GAUSSIAN):
+    """The forward pass of the iterations (no autograd) on the route of ``_route``; ``rel_eps``: the bound of the
+    plans, default PLAN_REL_EPS (only a plannable route plans; every other launch is dense, in the given order,
+    and drops nothing).  ``stacked``: the iterates, row sums and norms of all steps live in ONE buffer each
+    (``iterates_all`` (T+1,B,N,D), ``rsums_all`` / ``norms_all`` (T,B,N)) — what the row-restricted backward
+    gathers its rows from in three launches.
+    The Epanechnikov kernel neither reads nor moves the Gaussian calls' bookkeeping (_AUTO, CALLS, CALLS_W,
+    LAST_NEAREST); CALLS_EPA counts its calls."""
+    global CALLS_W, CALLS_EPA, LAST_PLAN_STATS, AUTO_STAT, LAST_NEAREST
     x = X.contiguous()
     B, N, D = x.shape
-    if ARITH not in _SPLIT and ARITH != "f32":
-        raise ValueError("PARSENET_MS_ARITH must be fp16x2, bf16x3 or f32, not %r" % ARITH)
-    if D != 128:
-        # (rel_eps bounds what a block-sparse plan may drop: the width kernels launch dense and drop nothing)
-        if kernel_width(D) != D:
-            raise ValueError("_run_iterations: width %d does not run as it is with PARSENET_MS_NARROW=%s and "
-                             "PARSENET_MS_ARITH=%s; mean_shift_iterations zero-pads it to %s"
-                             % (D, NARROW, ARITH, kernel_width(D)))
-        return _run_iterations_w(x, bsq, iterations, stacked)
-    kern = _SPLIT.get(ARITH) if iterations > 0 else None
-    sparse = kern is not None and ARITH == "bf16x3" and SPARSE_MIN_N <= N <= SPARSE_MAX_N and use_sparse(B, N)
-    if kern is not None and ARITH == "bf16x3":
+    route = _route(D, kind)
+    gaussian = kind == K.KERNEL_GAUSSIAN
+    if not gaussian:
+        CALLS_EPA += 1
+    elif route is _W:
+        CALLS_W += 1
+    # What makes operand and workspace.  Without a step to run that is not the route: a 128-wide Gaussian call has
+    # always made the exact route's packed copy and workspace then, whatever ARITH, every other call nothing
+    # (the backward of such a call: the exact route's workspace at 128); allocations and peak memory stay as they were.
+    set_up = route if iterations > 0 else _F32 if D == 128 and gaussian else None
+    plannable = route.plannable and gaussian and iterations > 0
+    sparse = plannable and SPARSE_MIN_N <= N <= SPARSE_MAX_N and use_sparse(B, N)
+    if plannable:
         CALLS["planned" if sparse else "dense"] += 1
     perm = inv = None
     if sparse:   # everything below runs on the locality-ordered points; undone on the way out
         perm = locality_order(x, int(os.environ.get("PARSENET_MS_LLOYD", "2")))
         inv = torch.empty_like(perm).scatter_(1, perm, torch.arange(N, device=x.device).expand(B, N))
         x = torch.gather(x, 1, perm.unsqueeze(2).expand(-1, -1, D))
-    x3 = kern[0](x) if kern is not None else None
-    # streamed copy of X: pre-split tile images (16-bit pieces) or channel-first fp32 (exact path)
-    xt = x3 if x3 is not None else K.meanshift_pack(x)
-    ws = K.MeanShiftWorkspace(B, N, D, x.device)
-    direct = stacked and ARITH == "bf16x3" and x3 is not None       # the bf16 x 3 kernels write into the buffers
+    operand = set_up.operand(x) if set_up is not None and set_up.operand is not None else None
+    ws = set_up.workspace(B, N, D, x.device, False) if set_up is not None else None
+    direct = stacked and route.writes_out       # the kernels write into the buffers
     it_all = rs_all = nr_all = None
     if direct:
         it_all = torch.empty((iterations + 1, B, N, D), dtype=torch.float32, device=x.device)
@@ -249,166 +325,84 @@ def _run_iterations(X, bsq, iterations, stacked=False, rel_eps=None):
     x_info = K.meanshift_x3_tileinfo(x) if sparse else None
     # (the plans of all iterations in one buffer: the auto mode's statistic is then one reduction, not one per plan)
     plans_buf, plan_slots, plan_core = K.meanshift_x3_plan_buffer(B, N, iterations, x.device) \
-        if sparse and iterations > 0 else (None, None, 0)
+        if sparse else (None, None, 0)
     q = x
     q_info = x_info          # (the first iterate IS the data: its caps are x_info)
     for it in range(iterations):
         out = (it_all[it + 1], rs_all[it], nr_all[it]) if direct else None
+        plan = None
         if sparse:
             plan = K.meanshift_x3_plan(q_info, x_info, bsq, N, PLAN_REL_EPS if rel_eps is None else rel_eps,
                                        out=plan_slots[it])
             plans.append(plan)
-            # (the caps of the new iterate — the next plan's, and the nearest-point search's at the end — come
-            # out of the launch that combines the partial results)
-            q, r, n, q_info = K.meanshift_x3_iter_fwd(q, x3, bsq, ws, plan, out=out, want_info=True)
-        elif x3 is not None and ARITH == "bf16x3":
-            q, r, n = K.meanshift_x3_iter_fwd(q, x3, bsq, ws, None, out=out)
-        elif x3 is not None:
-            q, r, n = kern[1](q, x3, bsq, ws)
-        else:
-            q, r, n = K.meanshift_iter_fwd(q, x, xt, bsq, ws)
+        # (planned: the caps of the new iterate — the next plan's, and the nearest-point search's at the end — come
+        # out of the launch that combines the partial results)
+        res = route.fwd(q, x, operand, bsq, ws, plan, out, sparse, kind)
+        q, r, n = res[:3]
+        if sparse:
+            q_info = res[3]
         iterates.append(q)
         rsums.append(r)
         norms.append(n)
-    global LAST_PLAN_STATS, AUTO_STAT, LAST_NEAREST
-    LAST_NEAREST = None
-    if sparse and WANT_NEAREST and iterations > 0:
+    if gaussian:
+        LAST_NEAREST = None
+    if sparse and WANT_NEAREST:
         LAST_NEAREST = K.meanshift_x3_nearest(x, q, x_info, q_info, perm)
     if sparse and os.environ.get("PARSENET_MS_STATS") == "1":
         LAST_PLAN_STATS = [K.meanshift_x3_plan_stats(p, B, N) for p in plans]
-    if sparse and SPARSE == "auto" and plans:
+    if sparse and SPARSE == "auto":
         AUTO_STAT = K.meanshift_x3_plan_visited((plans_buf, len(plans), plan_core), B, N)
     if stacked and not direct:
         it_all = torch.stack(iterates)
         rs_all = torch.stack(rsums) if rsums else torch.empty((0, B, N), device=x.device)
         nr_all = torch.stack(norms) if norms else torch.empty((0, B, N), device=x.device)
-    return {"x": x, "xt": xt, "x3": x3, "kern": kern, "sparse": sparse, "perm": perm, "inv": inv, "q": q,
-            "iterates": iterates, "rsums": rsums, "norms": norms, "plans": plans,
-            "iterates_all": it_all, "rsums_all": rs_all, "norms_all": nr_all}
-
-
-def _run_iterations_w(x, bsq, iterations, stacked):
-    """``_run_iterations`` on the width-32 / width-64 kernels: dense launches in the given order, the same
-    dict (no tile images, no plans: ``x3`` / ``xt`` / ``perm`` / ``inv`` are None)."""
-    global CALLS_W, LAST_NEAREST
-    B, N, D = x.shape
-    LAST_NEAREST = None
-    CALLS_W += 1
-    it_all = rs_all = nr_all = None
-    if stacked:
-        it_all = torch.empty((iterations + 1, B, N, D), dtype=torch.float32, device=x.device)
-        rs_all = torch.empty((iterations, B, N), dtype=torch.float32, device=x.device)
-        nr_all = torch.empty((iterations, B, N), dtype=torch.float32, device=x.device)
-        it_all[0].copy_(x)
-        x = it_all[0]
-    ws = K.MeanShiftWWorkspace(B, N, D, x.device) if iterations > 0 else None
-    iterates, rsums, norms = [x], [], []
-    q = x
-    for it in range(iterations):
-        out = (it_all[it + 1], rs_all[it], nr_all[it]) if stacked else None
-        q, r, n = K.meanshift_w_iter_fwd(q, x, bsq, ws, out=out)
-        iterates.append(q)
-        rsums.append(r)
-        norms.append(n)
-    return {"x": x, "xt": None, "x3": None, "kern": "w", "sparse": False, "perm": None, "inv": None, "q": q,
-            "iterates": iterates, "rsums": rsums, "norms": norms, "plans": [],
-            "iterates_all": it_all, "rsums_all": rs_all, "norms_all": nr_all}
-
-
-def _run_iterations_epa(X, bsq, iterations):
-    """``_run_iterations`` with the Epanechnikov kernel: dense launches in the given order at width 32, 64 or
-    128 (bf16 x 3), the same dict (no plans, no permutation)."""
-    global CALLS_EPA
-    x = X.contiguous()
-    B, N, D = x.shape
-    if ARITH != "bf16x3":
-        raise ValueError("the fused Epanechnikov kernel is bf16x3 only, PARSENET_MS_ARITH is %r "
-                         "(MeanShift.mean_shift_ runs the tensor expressions then)" % ARITH)
-    if D != 128 and kernel_width(D) != D:
-        raise ValueError("_run_iterations_epa: width %d does not run as it is; mean_shift_iterations zero-pads it "
-                         "to %s" % (D, kernel_width(D)))
-    CALLS_EPA += 1
-    narrow = D != 128
-    x3 = ws = None
-    if iterations > 0:
-        x3 = None if narrow else K.meanshift_x3_split(x)
-        ws = K.MeanShiftWWorkspace(B, N, D, x.device) if narrow else K.MeanShiftWorkspace(B, N, D, x.device)
-    iterates, rsums, norms = [x], [], []
-    q = x
-    for it in range(iterations):
-        if narrow:
-            q, r, n = K.meanshift_w_iter_fwd(q, x, bsq, ws, kind=K.KERNEL_EPANECHNIKOV)
-        else:
-            q, r, n = K.meanshift_x3_iter_fwd(q, x3, bsq, ws, None, kind=K.KERNEL_EPANECHNIKOV)
-        iterates.append(q)
-        rsums.append(r)
-        norms.append(n)
-    return {"x": x, "xt": x3, "x3": x3, "kern": "w" if narrow else _SPLIT["bf16x3"], "sparse": False, "perm": None,
-            "inv": None, "q": q, "iterates": iterates, "rsums": rsums, "norms": norms, "plans": [],
-            "iterates_all": None, "rsums_all": None, "norms_all": None}
+    st = _Iterations()
+    st.route, st.x, st.operand, st.sparse, st.perm, st.inv, st.q = route, x, operand, sparse, perm, inv, q
+    st.iterates, st.rsums, st.norms, st.plans = iterates, rsums, norms, plans
+    st.iterates_all, st.rsums_all, st.norms_all = it_all, rs_all, nr_all
+    return st
 
 
 class _MeanShiftIterations(torch.autograd.Function):
     """X (B,N,D) unit rows, bsq (B) squared bandwidths -> iterate after ``iterations`` steps.
-    Saves only the iterates, row sums and norms (O(T N D)); the backward recomputes the kernel.
-    ``kind``: the kernel profile (kernels.KERNEL_GAUSSIAN / KERNEL_EPANECHNIKOV) of forward and backward."""
+    Saves only the iterates, row sums and norms (O(T N D)); the backward recomputes the kernel on the route and
+    with the kernel profile ``kind`` (kernels.KERNEL_GAUSSIAN / KERNEL_EPANECHNIKOV) of the forward, whatever
+    the module's switches say by then."""
 
     @staticmethod
     def forward(ctx, X, bsq, iterations, kind=K.KERNEL_GAUSSIAN):
         D = X.shape[2]
-        if kind != K.KERNEL_GAUSSIAN:
-            st = _run_iterations_epa(X, bsq, iterations)
-        else:
-            st = _run_iterations(X, bsq, iterations, rel_eps=PLAN_REL_EPS_DENSE_BWD)   # (its backward reuses the plans)
-        sparse, q = st["sparse"], st["q"]
-        ctx.iterations = iterations
-        ctx.kind = kind
-        ctx.x3 = st["x3"]
-        ctx.kern = st["kern"]
-        ctx.sparse = sparse
-        ctx.narrow = st["kern"] == "w"
-        ctx.save_for_backward(st["xt"], bsq, *st["iterates"], *st["rsums"], *st["norms"], *st["plans"],
-                              *([st["perm"], st["inv"]] if sparse else []))
+        # (rel_eps: the backward reuses the plans)
+        st = _run_iterations(X, bsq, iterations, rel_eps=PLAN_REL_EPS_DENSE_BWD, kind=kind)
+        ctx.iterations, ctx.kind, ctx.route, ctx.sparse = iterations, kind, st.route, st.sparse
+        ctx.save_for_backward(st.operand, bsq, *st.iterates, *st.rsums, *st.norms, *st.plans,
+                              *([st.perm, st.inv] if st.sparse else []))
         if iterations == 0:
-            return st["x"].clone()
-        return torch.gather(q, 1, st["inv"].unsqueeze(2).expand(-1, -1, D)) if sparse else q
+            return st.x.clone()
+        return torch.gather(st.q, 1, st.inv.unsqueeze(2).expand(-1, -1, D)) if st.sparse else st.q
 
     @staticmethod
     def backward(ctx, gy):
-        T = ctx.iterations
+        T, route = ctx.iterations, ctx.route
         saved = ctx.saved_tensors
-        xt, bsq = saved[0], saved[1]
+        operand, bsq = saved[0], saved[1]
         iterates = saved[2:3 + T]
         rsums = saved[3 + T:3 + 2 * T]
         norms = saved[3 + 2 * T:3 + 3 * T]
-        plans = saved[3 + 3 * T:3 + 4 * T] if ctx.sparse else None
+        plans = saved[3 + 3 * T:3 + 4 * T] if ctx.sparse else [None] * T
         x = iterates[0]
         B, N, D = x.shape
         gX = torch.zeros_like(x)
         g = gy.contiguous()
-        if ctx.narrow:
-            ws = K.MeanShiftWWorkspace(B, N, D, x.device, backward=True) if T > 0 else None
-            for it in reversed(range(T)):
-                g = K.meanshift_w_iter_bwd(g, iterates[it + 1], iterates[it], x, rsums[it], norms[it], bsq, ws, gX,
-                                           kind=ctx.kind)
-            gX += g  # the first iterate is X itself
-            return gX, None, None, None
-        ws = K.MeanShiftWorkspace(B, N, D, x.device, backward=True, exact_f32=ctx.x3 is None)
+        # (no step: a 128-wide call takes the exact route's workspace, a narrower one none — see _run_iterations)
+        set_up = route if T > 0 else _F32 if D == 128 else None
+        ws = set_up.workspace(B, N, D, x.device, True) if set_up is not None else None
         if ctx.sparse:
             perm, inv = saved[-2], saved[-1]
             g = torch.gather(g, 1, perm.unsqueeze(2).expand(-1, -1, D))
         for it in reversed(range(T)):
-            if ctx.kind != K.KERNEL_GAUSSIAN:
-                g = K.meanshift_x3_iter_bwd(g, iterates[it + 1], iterates[it], x, ctx.x3, rsums[it], norms[it], bsq,
-                                            ws, gX, None, kind=ctx.kind)
-            elif ctx.sparse:
-                g = K.meanshift_x3_iter_bwd(g, iterates[it + 1], iterates[it], x, ctx.x3, rsums[it], norms[it], bsq,
-                                            ws, gX, plans[it])
-            elif ctx.x3 is not None:
-                g = ctx.kern[2](g, iterates[it + 1], iterates[it], x, ctx.x3, rsums[it], norms[it], bsq, ws, gX)
-            else:
-                g = K.meanshift_iter_bwd(g, iterates[it + 1], iterates[it], x, xt, rsums[it], norms[it], bsq,
-                                         ws, gX)
+            g = route.bwd(g, iterates[it + 1], iterates[it], x, operand, rsums[it], norms[it], bsq, ws, gX,
+                          plans[it], ctx.kind)
         gX += g  # the first iterate is X itself
         if ctx.sparse:
             gX = torch.gather(gX, 1, inv.unsqueeze(2).expand(-1, -1, D))
@@ -461,13 +455,12 @@ def mean_shift_iterations_state(X, b, iterations):
     bsq = (bt.detach() ** 2).contiguous()
     with torch.no_grad():
         st = _run_iterations(X.detach(), bsq, int(iterations), stacked=True)
-        q = st["q"]
-        new_X = torch.gather(q, 1, st["inv"].unsqueeze(2).expand(-1, -1, D)) if st["sparse"] else q
+        new_X = torch.gather(st.q, 1, st.inv.unsqueeze(2).expand(-1, -1, D)) if st.sparse else st.q
         if iterations == 0:
             new_X = new_X.clone()
     state = MeanShiftState()
-    state.x, state.bsq, state.inv, state.iterations, state.new_X = st["x"], bsq, st["inv"], int(iterations), new_X
-    state.iterates, state.rsums, state.norms = st["iterates_all"], st["rsums_all"], st["norms_all"]
+    state.x, state.bsq, state.inv, state.iterations, state.new_X = st.x, bsq, st.inv, int(iterations), new_X
+    state.iterates, state.rsums, state.norms = st.iterates_all, st.rsums_all, st.norms_all
     return new_X, state
 
 

@@ -107,12 +107,12 @@ def test_fused_epanechnikov_refuses_what_it_has_no_kernel_for(monkeypatch):
     """mean_shift_iterations is the fused path and nothing else: CPU tensors, other arithmetics and widths
     above 128 are errors there (MeanShift.mean_shift_ decides; it never gets this far with them)."""
     import torch
-    from parsenet_codebase_amd import mean_shift as MSM
+    from parsenet_codebase_amd import kernels as K, mean_shift as MSM
     monkeypatch.setattr(MSM, "ARITH", "bf16x3")
     with pytest.raises(RuntimeError):
         MSM.mean_shift_iterations(torch.zeros(40, 64), 0.5, 1, kernel_type="epa")
     with pytest.raises(ValueError):
-        MSM._run_iterations_epa(torch.zeros(1, 40, 50), torch.ones(1), 1)
+        MSM._run_iterations(torch.zeros(1, 40, 50), torch.ones(1), 1, kind=K.KERNEL_EPANECHNIKOV)
     monkeypatch.setattr(MSM, "ARITH", "f32")
     with pytest.raises(ValueError, match="bf16x3"):
-        MSM._run_iterations_epa(torch.zeros(1, 40, 128), torch.ones(1), 1)
+        MSM._run_iterations(torch.zeros(1, 40, 128), torch.ones(1), 1, kind=K.KERNEL_EPANECHNIKOV)

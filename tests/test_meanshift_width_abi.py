@@ -66,16 +66,16 @@ def test_iterations_refuse_a_width_the_switches_send_elsewhere(monkeypatch):
     """_run_iterations runs a width as it is: 64-wide rows under pad128 or the f32 arithmetic must not end on
     the bf16 x 3 width kernels behind the caller's back (mean_shift_iterations pads them to 128 first)."""
     import torch
-    from parsenet_codebase_amd import mean_shift as MSM
+    from parsenet_codebase_amd import kernels as K, mean_shift as MSM
     x, bsq = torch.zeros(1, 40, 64), torch.ones(1)
     monkeypatch.setattr(MSM, "ARITH", "bf16x3")
     monkeypatch.setattr(MSM, "NARROW", "pad128")
     with pytest.raises(ValueError, match="pad128"):
-        MSM._run_iterations(x, bsq, 1)
+        MSM._run_iterations(x, bsq, 1, kind=K.KERNEL_GAUSSIAN)
     monkeypatch.setattr(MSM, "NARROW", "native")
     monkeypatch.setattr(MSM, "ARITH", "f32")
     with pytest.raises(ValueError, match="f32"):
-        MSM._run_iterations(x, bsq, 1)
+        MSM._run_iterations(x, bsq, 1, kind=K.KERNEL_GAUSSIAN)
     monkeypatch.setattr(MSM, "ARITH", "bf16x3")
     with pytest.raises(ValueError):
-        MSM._run_iterations(torch.zeros(1, 40, 50), bsq, 1)
+        MSM._run_iterations(torch.zeros(1, 40, 50), bsq, 1, kind=K.KERNEL_GAUSSIAN)
