@@ -271,11 +271,19 @@ int pn_gemm_x3_wgrad_f32(const float* gy, const float* x, int B, int M, int K, i
  * unorm (B,R) the saved row sums and pre-normalisation norms of those rows, x (B,N,D) the data, bsq (B)
  * the squared bandwidths.  Writes gq (B,R,D), the gradient w.r.t. the input rows, and ADDS the step's
  * gradient w.r.t. the data into gx (B,N,D).  D in {32, 64, 128}.  No atomics.  workspace:
- * pn_meanshift_rows_bwd_workspace(B, N) bytes. */
+ * pn_meanshift_rows_bwd_workspace(B, N) bytes.
+ * _kind_: the same with the kernel profile of the forward pass as an argument (before `stream`), as in the
+ * _kind_ entry points above: PN_MS_KERNEL_GAUSSIAN is exactly pn_meanshift_rows_bwd_f32;
+ * PN_MS_KERNEL_EPANECHNIKOV recomputes K = max(0, 3/4 (1 - (2 - 2 q x^T) / b^2)) with dK = 3/2 / b^2 on the
+ * support and exactly 0 off it.  Same workspace, same launches.  Any other kind: PN_ERR_ARG. */
 size_t pn_meanshift_rows_bwd_workspace(int B, int N);
 int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum, const float* unorm,
                               const float* x, const float* bsq, int B, int N, int D, int R, float* gq, float* gx,
                               void* workspace, size_t workspace_bytes, void* stream);
+int pn_meanshift_rows_bwd_kind_f32(const float* gy, const float* y, const float* q, const float* rsum,
+                                   const float* unorm, const float* x, const float* bsq, int B, int N, int D, int R,
+                                   float* gq, float* gx, void* workspace, size_t workspace_bytes, int kind,
+                                   void* stream);
 /* gx[b, rows[b,r], :] += g[b, r, :], r ascending (rows (B,R) int64 may repeat; entries outside [0, N)
  * are skipped): the first iterate of the mean-shift iterations IS the data. */
 int pn_meanshift_rows_scatter_add_f32(const float* g, const int64_t* rows, int B, int N, int D, int R, float* gx,

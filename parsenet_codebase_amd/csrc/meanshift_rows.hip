@@ -30,6 +30,19 @@
 // 4-wave workgroup per CU and nothing hides its load -> barrier -> product -> barrier -> read-add-write chain;
 // the matrix-core version was removed again.
 //
+// Kernel profiles.  pn_ms_rows_bwd_kernel is a template on the profile MR_KIND as well (parsenet_hip.h:
+// PN_MS_KERNEL_GAUSSIAN, the above, operation for operation the kernel it was before the parameter existed /
+// PN_MS_KERNEL_EPANECHNIKOV).  The Epanechnikov form (src/mean_shift.py:64-68; the convention of the dense passes,
+// meanshift_w.hip's MSW_EPA) replaces three formulas of the 64 x 64 block and nothing else:
+//   K_ij  = max(0, 3/4 (1 - (2 - 2 q_i.x_j) / b^2))        no clamp, no exp2; zero past N
+//   gs_ij = K_ij > 0 ? 3/2 (gu_i.x_j - c_i) alpha_i : 0    dK/d(q.x) is 3/2 / b^2 on the support, exactly 0 off it
+//   K_ij / r_i of the gX term with that K
+// alpha = 1 / (r b^2) as for the Gaussian kernel, so pn_ms_rows_prep_kernel has no profile.  Off the support gs is a
+// select and K / r a product with an exact zero: the gX rows of points outside every row's support receive 0.0.
+// Staging, LDS (the sizes below), exclusive ownership of gX rows and the fixed-order gq reduction are shared;
+// the compiler reports 96 / 102 / 130 VGPRs at width 128 / 64 / 32 (Gaussian: 106 / 106 / 128) and no scratch.
+// Not timed.
+//
 // Widths.  The four kernels are templates on the embedding width MR_D (32, 64, 128) and the row stride MR_LD of the
 // staged operands; the entry points dispatch on D.  MR_LD = MR_D + 4 floats at every width: rows stay 16-byte
 // aligned, and the sixteen rows a 16-lane group of a ds_read_b128 touches start at 16-byte slots
@@ -112,7 +125,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_prep_kernel(const float* __res
   }
 }
 
-template <int MR_D, int MR_LD>
+template <int MR_D, int MR_LD, int MR_KIND>
 __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
     const float* __restrict__ gu, const float* __restrict__ scal, const float* __restrict__ q,
     const float* __restrict__ x, const float* __restrict__ bsq, int N, int R, int nblk, float* __restrict__ gx,
@@ -133,6 +146,7 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
   const int j0 = blk * MR_CB;
   const float bs = bsq[b];
   const float hl = (0.5f / bs) * MR_LOG2E;
+  const float ib = 1.0f / bs;       // (PN_MS_KERNEL_EPANECHNIKOV)
   const float* __restrict__ xb = x + (size_t)b * N * MR_D;
 
   // ---- stage: x rows (zero past N), q rows, gu rows + the per-row scalars
@@ -190,7 +204,8 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
           t[a][e] = __builtin_fmaf(uv[a].w, xv[e].w, t[a][e]);
         }
     }
-    // kernel values (meanshift.hip's MS_EW): exp2 of the clamped argument, zero past N
+    // kernel values, zero past N.  Gaussian (meanshift.hip's MS_EW): exp2 of the clamped argument; Epanechnikov
+    // (meanshift_w.hip's MSW_EPA): 3/4 of the positive part of 1 - dist / b^2, derivative 3/2 / b^2 on the support
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const int i = ti + 16 * a;
@@ -199,11 +214,18 @@ __global__ __launch_bounds__(256) void pn_ms_rows_bwd_kernel(
       for (int e = 0; e < 4; ++e) {
         const int j = tj + 16 * e;
         const float dist = __builtin_fmaf(-2.0f, s[a][e], 2.0f);
-        const float a2 = -dist * hl;
-        const float a2c = __builtin_amdgcn_fmed3f(a2, -MR_LIM2, MR_LIM2);
-        float kv = __builtin_amdgcn_exp2f(a2c);
-        if (j0 + j >= N) kv = 0.f;
-        const float g = a2c == a2 ? kv * ((t[a][e] - ci) * ai) : 0.f;
+        float kv, g;
+        if constexpr (MR_KIND == PN_MS_KERNEL_EPANECHNIKOV) {
+          kv = fmaxf(0.0f, 0.75f * __builtin_fmaf(-dist, ib, 1.0f));
+          if (j0 + j >= N) kv = 0.f;
+          g = kv > 0.0f ? 1.5f * ((t[a][e] - ci) * ai) : 0.f;
+        } else {
+          const float a2 = -dist * hl;
+          const float a2c = __builtin_amdgcn_fmed3f(a2, -MR_LIM2, MR_LIM2);
+          kv = __builtin_amdgcn_exp2f(a2c);
+          if (j0 + j >= N) kv = 0.f;
+          g = a2c == a2 ? kv * ((t[a][e] - ci) * ai) : 0.f;
+        }
         GS[i * MR_LG + j] = g;
         GT[j * MR_LG + i] = g;
         KR[i * MR_LG + j] = kv * ri;
@@ -348,16 +370,16 @@ extern "C" size_t pn_meanshift_rows_bwd_workspace(int B, int N) {
   return mr_part_bytes(B, N) + mr_gu_bytes(B) + pn_align_up((size_t)B * MR_R * 4 * sizeof(float), 256);
 }
 
-template <int MR_D>
+template <int MR_D, int MR_KIND>
 static int mr_rows_bwd(const float* gy, const float* y, const float* q, const float* rsum, const float* unorm,
                        const float* x, const float* bsq, int B, int N, int R, float* gq, float* gx, void* workspace,
                        hipStream_t stream) {
   constexpr int MR_LD = MR_LDOF(MR_D);
   const int nblk = pn_cdiv(N, MR_CB);
   const size_t lds_valu = (size_t)(3 * MR_R * MR_LD + 3 * MR_R * MR_LG + 3 * MR_R) * sizeof(float);
-  static unsigned attr_devs = 0;       // (one per instantiation)
+  static unsigned attr_devs = 0;       // (one per instantiation: width and kernel profile)
   if (pn_first_on_device(&attr_devs)) {
-    PN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pn_ms_rows_bwd_kernel<MR_D, MR_LD>),
+    PN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pn_ms_rows_bwd_kernel<MR_D, MR_LD, MR_KIND>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_valu));
   }
   float* part = static_cast<float*>(workspace);
@@ -367,7 +389,7 @@ static int mr_rows_bwd(const float* gy, const float* y, const float* q, const fl
     PN_PROF("meanshift_rows_bwd", stream);
     hipLaunchKernelGGL((pn_ms_rows_prep_kernel<MR_D, MR_LD>), dim3(MR_R / 4, B), dim3(256), 0, stream, gy, y, rsum, unorm,
                        bsq, R, gu, scal);
-    hipLaunchKernelGGL((pn_ms_rows_bwd_kernel<MR_D, MR_LD>), dim3(nblk, B), dim3(256), lds_valu, stream, (const float*)gu,
+    hipLaunchKernelGGL((pn_ms_rows_bwd_kernel<MR_D, MR_LD, MR_KIND>), dim3(nblk, B), dim3(256), lds_valu, stream, (const float*)gu,
                        (const float*)scal, q, x, bsq, N, R, nblk, gx, part);
   }
   PN_CHECK_LAUNCH();
@@ -379,22 +401,41 @@ static int mr_rows_bwd(const float* gy, const float* y, const float* q, const fl
 
 // One step of the row-restricted backward.  gy, y, q (B,R,D), rsum, unorm (B,R): the R rows of the
 // incoming gradient, of the step's result, of its input iterate and of its saved row sums / norms;
-// x (B,N,D) the data; bsq (B); D = 32, 64 or 128.  Writes gq (B,R,D) and ADDS the step's contribution into gx (B,N,D).
-extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum,
-                                         const float* unorm, const float* x, const float* bsq, int B, int N, int D,
-                                         int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
-                                         void* stream_) {
+// x (B,N,D) the data; bsq (B); D = 32, 64 or 128; kind: the kernel profile of the forward pass
+// (PN_MS_KERNEL_GAUSSIAN / PN_MS_KERNEL_EPANECHNIKOV).  Writes gq (B,R,D) and ADDS the step's contribution into gx (B,N,D).
+extern "C" int pn_meanshift_rows_bwd_kind_f32(const float* gy, const float* y, const float* q, const float* rsum,
+                                              const float* unorm, const float* x, const float* bsq, int B, int N, int D,
+                                              int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
+                                              int kind, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   PN_CHECK_ARG(D == 32 || D == 64 || D == 128, "pn_meanshift_rows_bwd_f32: D must be one of {32, 64, 128}, got %d", D);
   PN_CHECK_ARG(R >= 1 && R <= MR_R, "pn_meanshift_rows_bwd_f32: 1 <= R <= %d, got %d", MR_R, R);
   PN_CHECK_ARG(B >= 1 && N >= 1, "pn_meanshift_rows_bwd_f32: empty input");
+  PN_CHECK_ARG(kind == PN_MS_KERNEL_GAUSSIAN || kind == PN_MS_KERNEL_EPANECHNIKOV,
+               "pn_meanshift_rows_bwd_kind_f32: kernel kind %d unknown (0 Gaussian, 1 Epanechnikov)", kind);
   if (workspace_bytes < pn_meanshift_rows_bwd_workspace(B, N)) {
     pn_set_error("pn_meanshift_rows_bwd_f32: workspace too small");
     return PN_ERR_WORKSPACE;
   }
-  if (D == 32) return mr_rows_bwd<32>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
-  if (D == 64) return mr_rows_bwd<64>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
-  return mr_rows_bwd<128>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream);
+#define MR_CALL(D_, K_) mr_rows_bwd<D_, K_>(gy, y, q, rsum, unorm, x, bsq, B, N, R, gq, gx, workspace, stream)
+  if (kind == PN_MS_KERNEL_EPANECHNIKOV) {
+    if (D == 32) return MR_CALL(32, PN_MS_KERNEL_EPANECHNIKOV);
+    if (D == 64) return MR_CALL(64, PN_MS_KERNEL_EPANECHNIKOV);
+    return MR_CALL(128, PN_MS_KERNEL_EPANECHNIKOV);
+  }
+  if (D == 32) return MR_CALL(32, PN_MS_KERNEL_GAUSSIAN);
+  if (D == 64) return MR_CALL(64, PN_MS_KERNEL_GAUSSIAN);
+  return MR_CALL(128, PN_MS_KERNEL_GAUSSIAN);
+#undef MR_CALL
+}
+
+// ... with the Gaussian kernel
+extern "C" int pn_meanshift_rows_bwd_f32(const float* gy, const float* y, const float* q, const float* rsum,
+                                         const float* unorm, const float* x, const float* bsq, int B, int N, int D,
+                                         int R, float* gq, float* gx, void* workspace, size_t workspace_bytes,
+                                         void* stream_) {
+  return pn_meanshift_rows_bwd_kind_f32(gy, y, q, rsum, unorm, x, bsq, B, N, D, R, gq, gx, workspace, workspace_bytes,
+                                        PN_MS_KERNEL_GAUSSIAN, stream_);
 }
 
 extern "C" int pn_meanshift_rows_scatter_add_f32(const float* g, const int64_t* rows, int B, int N, int D, int R,

@@ -942,7 +942,7 @@ class Evaluation:
                 break
         return center, bandwidth, cluster_ids
 
-    def prefetch_clustering(self, embedding_b, quantile, iterations):
+    def prefetch_clustering(self, embedding_b, quantile, iterations, kernel_type="gaussian"):
         """Queue the clustering of ONE shape (normalisation, bandwidth, mean-shift iterations) on
         the current stream without a host synchronisation and return a handle for
         ``fitting_loss(prefetched=[handle])``.  Lets a caller run shape b+1's iterations on a side
@@ -950,10 +950,10 @@ class Evaluation:
         emb = torch.nn.functional.normalize(embedding_b, p=2, dim=-1)
         if emb.shape[0] > 10000:      # the bandwidth would depend on the shuffle: synchronous path
             return {"emb": emb, "new_X": None, "bw": None, "flag": None}
-        new_X, bw, flag = self.ms.shift_async(emb, 10000, quantile, iterations)
+        new_X, bw, flag = self.ms.shift_async(emb, 10000, quantile, iterations, kernel_type=kernel_type)
         return {"emb": emb, "new_X": new_X, "bw": bw, "flag": flag}
 
-    def _clusters(self, emb_b, quantile, iterations, handle):
+    def _clusters(self, emb_b, quantile, iterations, handle, kernel_type="gaussian"):
         if handle is not None and handle["new_X"] is not None:
             done = self.ms.finish(handle["emb"], handle["new_X"], handle["bw"], handle["flag"])
             if done is not None:
@@ -961,14 +961,17 @@ class Evaluation:
                 if not (center.shape[0] > 49 and torch.unique(cluster_ids).shape[0] > 49):
                     return center, bandwidth, cluster_ids
                 quantile *= 1.2          # the guard's retry, on the synchronous path
-        return self.guard_mean_shift(emb_b, quantile, iterations, kernel_type="gaussian")
+        return self.guard_mean_shift(emb_b, quantile, iterations, kernel_type=kernel_type)
 
     def fitting_loss(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                     quantile=0.125, iterations=5, lamb=1.0, debug=False, eval=False, prefetched=None):
+                     quantile=0.125, iterations=5, lamb=1.0, debug=False, eval=False, prefetched=None,
+                     kernel_type="gaussian"):
         """embedding (B,N,128), points/normals (B,N,3) tensors; labels, primitives (B,N) integer
         arrays; primitives_log_prob (B,10,N).  Returns ([Loss, geometric mean, spline mean, s_iou,
         p_iou], [parameters, cluster ids, weights]) of the last shape, like the reference (which
-        is written for B = 1).  ``prefetched``: per-shape handles of ``prefetch_clustering``.
+        is written for B = 1).  ``prefetched``: per-shape handles of ``prefetch_clustering`` (made with the same
+        ``kernel_type``).  ``kernel_type``: the kernel of the mean-shift iterations — "gaussian" (the reference's
+        choice, src/residual_utils.py:113), or anything else for the Epanechnikov kernel — on every path below.
 
         Training calls (not eval / debug / prefetched) go through the STAGE-WISE path by default
         (``self.batched``: fitting_batch.fitting_losses_train — same decisions and arithmetic,
@@ -979,7 +982,8 @@ class Evaluation:
         if self.batched and eval and prefetched is None and not debug:
             # evaluation mode, stage by stage over all shapes and segments (fitting_eval.py)
             return self.fitting_losses_eval(embedding, points, normals, labels, primitives, primitives_log_prob,
-                                            quantile=quantile, iterations=iterations, lamb=lamb)[-1]
+                                            quantile=quantile, iterations=iterations, lamb=lamb,
+                                            kernel_type=kernel_type)[-1]
         if self.batched and not eval and prefetched is None and not debug:
             if embedding.shape[0] > 1 and not getattr(self, "_warned_last_only", False):
                 import warnings
@@ -987,7 +991,8 @@ class Evaluation:
                               "only (reference behaviour); call fitting_losses for all of them" % embedding.shape[0])
                 self._warned_last_only = True
             return self.fitting_losses(embedding, points, normals, labels, primitives, primitives_log_prob,
-                                       quantile=quantile, iterations=iterations, lamb=lamb)[-1]
+                                       quantile=quantile, iterations=iterations, lamb=lamb,
+                                       kernel_type=kernel_type)[-1]
         batch_size = embedding.shape[0]
         if prefetched is None:
             embedding = torch.nn.functional.normalize(embedding, p=2, dim=2)
@@ -999,16 +1004,18 @@ class Evaluation:
         loss = parameters = cluster_ids = weights = None
         for b in range(batch_size):
             center, bandwidth, cluster_ids = self._clusters(embedding[b], quantile, iterations,
-                                                            prefetched[b] if prefetched is not None else None)
+                                                            prefetched[b] if prefetched is not None else None,
+                                                            kernel_type=kernel_type)
             weights = center @ torch.transpose(embedding[b], 1, 0)
             if not eval:
                 loss, parameters, _, rows, cols, distance = self.residual_train_mode(
-                    points[b], normals[b], labels[b], cluster_ids, primitives[b], weights, bandwidth, lamb=lamb)
+                    points[b], normals[b], labels[b], cluster_ids, primitives[b], weights, bandwidth, lamb=lamb,
+                    kernel_type=kernel_type)
             else:
                 with torch.no_grad():
                     loss, parameters, _ = self.residual_eval_mode(
                         points[b], normals[b], labels[b], cluster_ids, primitives[b], prim_pred[b], weights,
-                        bandwidth, lamb=lamb, sample_points=False, if_optimize=False)
+                        bandwidth, lamb=lamb, sample_points=False, if_optimize=False, kernel_type=kernel_type)
                 # in the eval mode the memberships are the hard selection
                 ids_np = cluster_ids.data.cpu().numpy()
                 weights = to_one_hot(ids_np, np.unique(ids_np).shape[0], device_id=points.device.index).T
@@ -1019,7 +1026,7 @@ class Evaluation:
         return loss, [parameters, cluster_ids.data.cpu().numpy(), weights]
 
     def fitting_losses(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                       quantile=0.125, iterations=5, lamb=1.0, defer_metrics=False):
+                       quantile=0.125, iterations=5, lamb=1.0, defer_metrics=False, kernel_type="gaussian"):
         """Training-mode ``fitting_loss`` of EVERY shape of the batch (the reference's function
         returns the last shape's): a list of ([Loss, geometric mean, spline mean, s_iou, p_iou],
         [parameters, cluster ids, weights]), computed stage by stage over all shapes and segments
@@ -1030,10 +1037,10 @@ class Evaluation:
         from .fitting_batch import fitting_losses_train
         require_cuda(embedding, points, normals)
         return fitting_losses_train(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                                    quantile, iterations, lamb, defer_metrics)
+                                    quantile, iterations, lamb, defer_metrics, kernel_type)
 
     def fitting_losses_eval(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                            quantile=0.125, iterations=5, lamb=1.0, if_optimize=False):
+                            quantile=0.125, iterations=5, lamb=1.0, if_optimize=False, kernel_type="gaussian"):
         """Evaluation-mode ``fitting_loss`` (src/residual_utils.py:210-331: hard memberships, the modal
         predicted type, outlier removal and re-sampling of spline segments, sqrt residuals; ``if_optimize``:
         the LS refit of src/primitive_forward.py:153-296) of EVERY shape of the batch, stage by stage over
@@ -1042,21 +1049,21 @@ class Evaluation:
         from .fitting_eval import fitting_losses_eval
         require_cuda(embedding, points, normals)
         return fitting_losses_eval(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                                   quantile, iterations, lamb, if_optimize)
+                                   quantile, iterations, lamb, if_optimize, kernel_type)
 
     def reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw=0.01,
                           if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000,
-                          surface_distance=False):
+                          surface_distance=False, kernel_type="gaussian"):
         """test.py:108-185 for B shapes from given cluster ids: parameters, trimmed surfaces, samples and the table of
         seg-IoU, type-IoU, s-cover, p-cover and CD per shape, stage by stage (fitting_eval.reconstruct_batch).  The
         trimmed surfaces of the LS refit (``if_optimize=True``) are available here only.  ``surface_distance`` adds
         the coverage against the surfaces themselves (p_cover_surface, p_dist_surface)."""
         from .fitting_eval import reconstruct_batch
         return reconstruct_batch(self, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw,
-                                 if_optimize, if_visualize, epsilon, n_samples, surface_distance)
+                                 if_optimize, if_visualize, epsilon, n_samples, surface_distance, kernel_type)
 
     def fitting_losses_pipelined(self, embedding, points, normals, labels, primitives, primitives_log_prob,
-                                 quantile=0.125, iterations=5, lamb=1.0, chunks=2):
+                                 quantile=0.125, iterations=5, lamb=1.0, chunks=2, kernel_type="gaussian"):
         """``fitting_losses(defer_metrics=True)`` with the batch cut into ``chunks`` groups whose
         clustering is queued up front, so that the device works on the next group while the host
         matches the previous one (fitting_batch.fitting_losses_train_pipelined).  Returns
@@ -1064,9 +1071,12 @@ class Evaluation:
         from .fitting_batch import fitting_losses_train_pipelined
         require_cuda(embedding, points, normals)
         return fitting_losses_train_pipelined(self, embedding, points, normals, labels, primitives,
-                                              primitives_log_prob, quantile, iterations, lamb, chunks)
+                                              primitives_log_prob, quantile, iterations, lamb, chunks, kernel_type)
 
-    def residual_train_mode(self, points, normals, labels, cluster_ids, primitives, weights, bw, lamb=1.0):
+    def residual_train_mode(self, points, normals, labels, cluster_ids, primitives, weights, bw, lamb=1.0,
+                            kernel_type="gaussian"):
+        """src/residual_utils.py:154-208 from given cluster ids and memberships.  ``kernel_type``: the kernel the
+        clustering ran with (what ``fitting_loss`` hands through); nothing here depends on the kernel profile."""
         if not isinstance(cluster_ids, np.ndarray):
             cluster_ids = cluster_ids.data.cpu().numpy()
         rows, cols, unique_target, unique_pred = match(labels, cluster_ids)
@@ -1088,7 +1098,7 @@ class Evaluation:
 
     def residual_eval_mode(self, points, normals, labels, cluster_ids, primitives, pred_primitives, weights,
                            bw, lamb=1.0, sample_points=False, if_optimize=False, if_visualize=False,
-                           epsilon=None):
+                           epsilon=None, kernel_type="gaussian"):
         """src/residual_utils.py:210-331: residual error with HARD memberships.  Every predicted
         segment is fitted on its own points with the modal predicted primitive type (smallest on
         ties, scipy.stats.mode), splines after outlier removal and re-sampling; distances are
@@ -1097,7 +1107,8 @@ class Evaluation:
         empty), its own points stand in for the ground truth, and Loss is [].  ``sample_points``: the third result is
         the list of trimmed surfaces (surface.TrimmedSurface, one per fitted segment; ``epsilon`` overrides the
         per-type occupancy thresholds) that segment_utils.sample_from_collection_of_mesh samples — test.py:126-168.
-        Together with ``if_optimize`` it raises NotImplementedError."""
+        Together with ``if_optimize`` it raises NotImplementedError.  ``kernel_type``: the kernel the clustering
+        ran with (what ``fitting_loss`` hands through); hard memberships do not depend on the kernel profile."""
         if sample_points and if_optimize:
             raise NotImplementedError(_NO_REFIT_GRIDS)
         if not isinstance(cluster_ids, np.ndarray):

@@ -491,13 +491,14 @@ def siou_matched_segments_fast(match, prim_pred_per_cluster, primitives):
 # the stage
 # -------------------------------------------------------------------------------------------
 def fitting_losses_train(ev, embedding, points, normals, labels, primitives, primitives_log_prob, quantile,
-                         iterations, lamb, defer_metrics=False):
+                         iterations, lamb, defer_metrics=False, kernel_type="gaussian"):
     """Training-mode Evaluation.fitting_loss for every shape of the batch.  Returns a list (one
     entry per shape) of ([Loss, geometric mean, spline mean, s_iou, p_iou], [parameters, cluster
     ids, weights]) exactly as the reference's call with that single shape would.
-    ``ev``: the owning fitting.Evaluation (SplineNets, mean-shift object, slow-path helpers)."""
+    ``ev``: the owning fitting.Evaluation (SplineNets, mean-shift object, slow-path helpers).
+    ``kernel_type``: the kernel of the mean-shift iterations ("gaussian", or anything else for Epanechnikov)."""
     stage = _fitting_stage(ev, embedding, points, normals, labels, primitives, primitives_log_prob, quantile,
-                           iterations, lamb, defer_metrics)
+                           iterations, lamb, defer_metrics, kernel_type)
     next(stage)                      # clustering queued, the cluster-id download under way
     try:
         next(stage)                  # host matching, fits, losses
@@ -507,7 +508,7 @@ def fitting_losses_train(ev, embedding, points, normals, labels, primitives, pri
 
 
 def fitting_losses_train_pipelined(ev, embedding, points, normals, labels, primitives, primitives_log_prob, quantile,
-                                   iterations, lamb, chunks=2):
+                                   iterations, lamb, chunks=2, kernel_type="gaussian"):
     """The same stage for a batch cut into ``chunks`` groups of shapes, software-pipelined: the
     clustering of EVERY group is queued first (bandwidth, ten mean-shift iterations, NMS,
     memberships, and the stream-ordered copy of its cluster ids into pinned memory), only then
@@ -523,7 +524,8 @@ def fitting_losses_train_pipelined(ev, embedding, points, normals, labels, primi
     bounds = [(B * c // chunks, B * (c + 1) // chunks) for c in range(chunks)]
     labels, primitives = np.asarray(labels), np.asarray(primitives)
     stages = [_fitting_stage(ev, embedding[lo:hi], points[lo:hi], normals[lo:hi], labels[lo:hi], primitives[lo:hi],
-                             primitives_log_prob[lo:hi], quantile, iterations, lamb, True) for lo, hi in bounds]
+                             primitives_log_prob[lo:hi], quantile, iterations, lamb, True, kernel_type)
+              for lo, hi in bounds]
     for st in stages:
         next(st)
     parts = []
@@ -545,11 +547,12 @@ def fitting_losses_train_pipelined(ev, embedding, points, normals, labels, primi
 
 
 def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitives_log_prob, quantile, iterations,
-                   lamb, defer_metrics):
+                   lamb, defer_metrics, kernel_type="gaussian"):
     """Generator behind the two functions above: runs up to the point where the host needs the
     cluster ids (their copy into pinned memory is queued, an event recorded), yields ONCE, and on
     resumption waits for that copy and does the rest.  Returns (via StopIteration) what
-    fitting_losses_train returns."""
+    fitting_losses_train returns.  ``kernel_type`` reaches the iterations, the centre-rows backward and the
+    per-shape fallback; bandwidth, NMS, memberships and labels do not depend on the kernel profile."""
     B, N, D = embedding.shape
     dev = embedding.device
     labels, primitives = np.asarray(labels), np.asarray(primitives)
@@ -563,8 +566,8 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
     # The batched path at every width the mean-shift kernels serve (MSM.kernel_width: 32, 64, 128; with
     # PARSENET_MS_NARROW=pad128 always 128): a narrower embedding is zero-padded ONCE, here — the pad is
     # differentiable, zero columns are exact in every product and survive the renormalisation — and bandwidth,
-    # iterations, NMS, centre rows, memberships and labels all run at width W.  Narrow widths have no plans:
-    # LAST_NEAREST is then None and nms_batch takes its dot_select branch.
+    # iterations, NMS, centre rows, memberships and labels all run at width W.  Narrow widths and the Epanechnikov
+    # kernel have no plans: LAST_NEAREST is then None and nms_batch takes its dot_select branch.
     W = MSM.kernel_width(D)
     embw = emb if W is None or W == D else torch.nn.functional.pad(emb, (0, W - D))
     state = None
@@ -581,9 +584,9 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
                 # MSM.centre_rows below — and the backward then runs those rows alone; PARSENET_MS_ROWS_BWD=0:
                 # the dense backward passes over all rows, same gradient up to the summation order)
                 if ROWS_BWD:
-                    new_X, ms_state = MSM.mean_shift_iterations_state(embw, bw, iterations)
+                    new_X, ms_state = MSM.mean_shift_iterations_state(embw, bw, iterations, kernel_type=kernel_type)
                 else:
-                    new_X, ms_state = MSM.mean_shift_iterations(embw, bw, iterations), None
+                    new_X, ms_state = MSM.mean_shift_iterations(embw, bw, iterations, kernel_type=kernel_type), None
             finally:
                 MSM.WANT_NEAREST = False
             nearest, MSM.LAST_NEAREST = MSM.LAST_NEAREST, None
@@ -691,7 +694,7 @@ def _fitting_stage(ev, embedding, points, normals, labels, primitives, primitive
             all_fast = False
             CALLS_STAGE["per_shape"] += 1
             q = quantile * 1.2 if (fast and ncl_h[b] > 49) else quantile
-            c, bwb, ids = ev.guard_mean_shift(emb[b], q, iterations, kernel_type="gaussian")
+            c, bwb, ids = ev.guard_mean_shift(emb[b], q, iterations, kernel_type=kernel_type)
             centers.append(c)
             bws.append(bwb.reshape(()))
             cluster_ids.append(ids.cpu().numpy().astype(np.int64))

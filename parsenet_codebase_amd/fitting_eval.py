@@ -54,13 +54,14 @@ _REFIT = {"open": dict(size_u=20, size_v=20, up=(1600, 2000), sub=1600, degree=2
 CALLS_CLUSTER = {"batched": 0, "per_shape": 0}      # shapes by the branch of cluster_shapes that clustered them
 
 
-def cluster_shapes(ev, emb, quantile, iterations):
+def cluster_shapes(ev, emb, quantile, iterations, kernel_type="gaussian"):
     """guard_mean_shift of every shape (src/residual_utils.py:69-84) -> (clusters, calls): clusters[b] =
     (centres (C,128), bandwidth (0-dim tensor), cluster ids (N,) int64 numpy), calls[b] = the number of
     mean-shift calls the guard needed for shape b.  The fast path is fitting_batch's: one batched bandwidth
     selection, the iterations of all shapes per launch, NMS and labels on the device, one download; a shape
     with flagged selection rows or more than 49 clusters goes through the per-shape API (the guard's retry
-    with quantile x 1.2).
+    with quantile x 1.2).  ``kernel_type``: the kernel of the iterations on both branches ("gaussian", or
+    anything else for Epanechnikov); bandwidth, NMS and labels do not depend on it.
 
     numpy's generator is left where it was: the reference shuffles once per mean-shift call
     (src/mean_shift.py:121-122; every row is a sample, so the shuffle does not change the result) and the
@@ -78,7 +79,7 @@ def cluster_shapes(ev, emb, quantile, iterations):
             bw, bwflag = bwres
             MSM.WANT_NEAREST = True
             try:
-                new_X, _ = MSM.mean_shift_iterations_state(embw, bw, iterations)
+                new_X, _ = MSM.mean_shift_iterations_state(embw, bw, iterations, kernel_type=kernel_type)
             finally:
                 MSM.WANT_NEAREST = False
             nearest, MSM.LAST_NEAREST = MSM.LAST_NEAREST, None
@@ -103,7 +104,7 @@ def cluster_shapes(ev, emb, quantile, iterations):
         CALLS_CLUSTER["per_shape"] += 1
         q, n = (quantile * 1.2, 1) if ok else (quantile, 0)
         while True:
-            _, center, bandwidth, ids = ev.ms.mean_shift(emb[b], 10000, q, iterations, kernel_type="gaussian")
+            _, center, bandwidth, ids = ev.ms.mean_shift(emb[b], 10000, q, iterations, kernel_type=kernel_type)
             n += 1
             if center.shape[0] > 49 and torch.unique(ids).shape[0] > 49:
                 q *= 1.2
@@ -507,10 +508,10 @@ def fit_stage(ev, points, normals, seglists, ids_dev, if_optimize, stream, plane
 
 
 def fitting_losses_eval(ev, embedding, points, normals, labels, primitives, primitives_log_prob, quantile, iterations,
-                        lamb, if_optimize=False):
+                        lamb, if_optimize=False, kernel_type="gaussian"):
     """Evaluation-mode Evaluation.fitting_loss for every shape of the batch: a list (one entry per shape) of
     ([Loss, geometric mean, spline mean, s_iou, p_iou], [parameters, cluster ids, weights]) as the reference's
-    call with that single shape returns them."""
+    call with that single shape returns them.  ``kernel_type``: the kernel of the clustering (cluster_shapes)."""
     from .fitting import SIOU_matched_segments, to_one_hot
     B, N, D = embedding.shape
     dev = embedding.device
@@ -520,7 +521,7 @@ def fitting_losses_eval(ev, embedding, points, normals, labels, primitives, prim
         emb = torch.nn.functional.normalize(embedding.detach(), p=2, dim=2)
         prim_pred = torch.max(primitives_log_prob, 1)[1].data.cpu().numpy()
         with record_function("eval:clustering"):
-            clusters, ms_calls = cluster_shapes(ev, emb, quantile, iterations)
+            clusters, ms_calls = cluster_shapes(ev, emb, quantile, iterations, kernel_type=kernel_type)
         seglists = [eval_segments(labels[b], clusters[b][2], prim_pred[b])[0] for b in range(B)]
         ids_dev = h2d(np.stack([c[2] for c in clusters]).astype(np.int64), dev)           # (B,N)
         st = fit_stage(ev, points, normals, seglists, ids_dev, if_optimize, _ShuffleStream(ms_calls, N))
@@ -804,7 +805,8 @@ def _device_rows(rows, whole, given, dev):
 
 
 def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred_primitives, seeds, bw=0.01,
-                      if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000, surface_distance=False):
+                      if_optimize=False, if_visualize=True, epsilon=None, n_samples=10000, surface_distance=False,
+                      kernel_type="gaussian"):
     """What test.py:108-185 computes for one shape — residual_eval_mode(sample_points=True), the trimmed surfaces,
     sample_from_collection_of_mesh, the coverage figures and the IoUs — for B shapes, stage by stage: the fitting
     stage of this module from the GIVEN cluster ids (no embedding, no mean-shift), the analytic grids on the host in
@@ -816,7 +818,9 @@ def reconstruct_batch(ev, points, normals, labels, cluster_ids, primitives, pred
     points / normals: (B,N,3) or lists of (N_b,3), arrays or tensors; labels, cluster_ids, primitives,
     pred_primitives: integer arrays per shape; seeds: one integer per shape (the random-number contract:
     ShapeStreams; a batch equals the shape-by-shape loop under the same seeds, the caller's global state is restored).
-    ``bw`` is accepted for the reference's signature: hard memberships do not depend on it.
+    ``bw`` is accepted for the reference's signature: hard memberships do not depend on it.  ``kernel_type`` (last)
+    is the kernel the given cluster ids were made with (cluster_shapes): a caller hands one set of clustering
+    arguments to both; nothing after the clustering depends on the kernel profile.
     Returns one dict per shape: parameters (as residual_eval_mode), surfaces ([TrimmedSurface]), samples ((M_b,3) fp32
     on the device), metrics (sk_1, sk_2, sk, pk_1, pk_2, pk, cd, s_iou, p_iou) — or metrics None, samples None and
     ``message`` when the sampling of that shape fails (no surface with a kept cell, or none that gets more than 10

@@ -847,10 +847,11 @@ def gemm_x3_wgrad(gy, x, want_bias=False):
     return (gw, gb) if want_bias else gw
 
 
-def meanshift_rows_bwd(gy, y, q, rsum, unorm, x, bsq, gx, ws=None):
+def meanshift_rows_bwd(gy, y, q, rsum, unorm, x, bsq, gx, ws=None, kind=KERNEL_GAUSSIAN):
     """One step of the mean-shift backward restricted to R <= 64 rows per batch item (csrc/meanshift_rows.hip;
     src/mean_shift.py:45-79 maps every row on its own): gy, y, q (B,R,D), rsum, unorm (B,R), x (B,N,D),
-    bsq (B); D = 32, 64 or 128.  Returns gq (B,R,D); ADDS the step's gradient w.r.t. the data into gx (B,N,D)."""
+    bsq (B); D = 32, 64 or 128.  Returns gq (B,R,D); ADDS the step's gradient w.r.t. the data into gx (B,N,D).
+    ``kind``: the kernel profile of the forward pass (KERNEL_GAUSSIAN / KERNEL_EPANECHNIKOV)."""
     require_cuda(gy, y, q, rsum, unorm, x, bsq, gx)
     gy, y, q, x = _f32c(gy, "gy"), _f32c(y, "y"), _f32c(q, "q"), _f32c(x, "x")
     rsum, unorm, bsq = _f32c(rsum, "rsum"), _f32c(unorm, "unorm"), _f32c(bsq, "bsq")
@@ -868,9 +869,10 @@ def meanshift_rows_bwd(gy, y, q, rsum, unorm, x, bsq, gx, ws=None):
         ws = torch.empty(wsz, dtype=torch.uint8, device=x.device)
     gq = torch.empty_like(q)
     with _lib.on_device(x.device):
-        rc = lib.pn_meanshift_rows_bwd_f32(ptr(gy), ptr(y), ptr(q), ptr(rsum), ptr(unorm), ptr(x), ptr(bsq), B, N, D, R,
-                                           ptr(gq), ptr(gx), ptr(ws), ws.numel(), current_stream(x.device))
-    check(rc, "pn_meanshift_rows_bwd_f32")
+        rc = lib.pn_meanshift_rows_bwd_kind_f32(ptr(gy), ptr(y), ptr(q), ptr(rsum), ptr(unorm), ptr(x), ptr(bsq), B, N,
+                                                D, R, ptr(gq), ptr(gx), ptr(ws), ws.numel(), int(kind),
+                                                current_stream(x.device))
+    check(rc, "pn_meanshift_rows_bwd_kind_f32")
     return gq
 
 

@@ -90,7 +90,13 @@ LAST_NEAREST = None
 # counts its calls.  It exists in bf16 x 3 arithmetic only: ``MeanShift.mean_shift_`` sends an Epanechnikov
 # call to it for float32 GPU tensors of width <= 128 under PARSENET_MS_ARITH = bf16x3 and keeps the tensor
 # expressions (N x N per iteration, any device and dtype) for everything else, so the arithmetic asked for
-# is the arithmetic that runs.  mean_shift_iterations_state / centre_rows / shift_async are Gaussian-only.
+# is the arithmetic that runs.  mean_shift_iterations_state / centre_rows / shift_async — what the fitting stages
+# are built on — take the kernel type as well: the state's forward is the same dense fused route (no plan, no
+# locality order, ``inv`` None, counted by CALLS_EPA; with WANT_NEAREST set LAST_NEAREST comes out None and the
+# NMS selects for itself), the state records the profile, and the centre-rows backward runs the Epanechnikov
+# instantiation of csrc/meanshift_rows.hip.  These three have no tensor-expression form to keep: an Epanechnikov
+# call of them under another arithmetic, or with tensors that are not float32 on the GPU, is a ValueError that
+# names the arithmetic — never another arithmetic behind the caller's back.
 NARROW = os.environ.get("PARSENET_MS_NARROW", "native")
 NARROW_WIDTHS = (32, 64)
 CALLS_W = 0                 # calls of the iterations that ran on the width-32 / width-64 kernels
@@ -409,12 +415,26 @@ class _MeanShiftIterations(torch.autograd.Function):
         return gX, None, None, None
 
 
+def _kind_of(kernel_type):
+    """"gaussian", or anything else for the Epanechnikov kernel, as in the reference (src/mean_shift.py:59-68)."""
+    return K.KERNEL_GAUSSIAN if kernel_type == "gaussian" else K.KERNEL_EPANECHNIKOV
+
+
+def _require_fused_epanechnikov(who, X):
+    """The Epanechnikov form of ``who`` exists on the fused kernels alone: bf16x3 arithmetic, float32 on the GPU."""
+    if ARITH != "bf16x3":
+        raise ValueError("%s: the fused Epanechnikov kernel is bf16x3 only, PARSENET_MS_ARITH is %r" % (who, ARITH))
+    if not X.is_cuda or X.dtype != torch.float32:
+        raise ValueError("%s: the fused Epanechnikov kernel (bf16x3 arithmetic) takes float32 tensors on the GPU, "
+                         "got %s on %s" % (who, X.dtype, X.device))
+
+
 def mean_shift_iterations(X, b, iterations, kernel_type="gaussian"):
     """X (N,D) or (B,N,D), D <= 128; b scalar / 0-dim tensor / (B,) tensor of bandwidths.  Widths without
     kernels of their own run zero-padded to the next width that has them (``kernel_width``).  ``kernel_type``:
     "gaussian", or anything else for the Epanechnikov kernel as in the reference (bf16x3 arithmetic only)."""
     require_cuda(X)
-    kind = K.KERNEL_GAUSSIAN if kernel_type == "gaussian" else K.KERNEL_EPANECHNIKOV
+    kind = _kind_of(kernel_type)
     squeeze = X.dim() == 2
     Xb = X.unsqueeze(0) if squeeze else X
     B, D = Xb.shape[0], Xb.shape[2]
@@ -436,15 +456,21 @@ def mean_shift_iterations(X, b, iterations, kernel_type="gaussian"):
 class MeanShiftState:
     """What a forward pass of the iterations leaves behind for the row-restricted backward
     (``mean_shift_iterations_state`` / ``centre_rows``)."""
-    __slots__ = ("x", "bsq", "iterates", "rsums", "norms", "inv", "iterations", "new_X")
+    __slots__ = ("x", "bsq", "iterates", "rsums", "norms", "inv", "iterations", "new_X", "kind")
 
 
-def mean_shift_iterations_state(X, b, iterations):
+def mean_shift_iterations_state(X, b, iterations, kernel_type="gaussian"):
     """The iterations WITHOUT an autograd graph: returns (new_X (B,N,D) detached, state).  The training
     path reads the final iterate at the cluster centres only; ``centre_rows(X, state, ids)`` returns those
     rows WITH the gradient path back to X.  D is a width the kernels run at as it is (``kernel_width(D) == D``:
     128, and 32 / 64 on the width kernels); nothing is padded here — the caller pads once and keeps the padded
-    tensor for ``centre_rows`` and everything after it."""
+    tensor for ``centre_rows`` and everything after it.  ``kernel_type``: as ``mean_shift_iterations``; the
+    Epanechnikov forward is dense and in the given order (``state.inv`` is None), and with WANT_NEAREST set it
+    leaves LAST_NEAREST None."""
+    global LAST_NEAREST
+    kind = _kind_of(kernel_type)
+    if kind != K.KERNEL_GAUSSIAN:
+        _require_fused_epanechnikov("mean_shift_iterations_state", X)
     require_cuda(X)
     if X.dim() != 3:
         raise ValueError("mean_shift_iterations_state expects (B,N,D)")
@@ -454,13 +480,16 @@ def mean_shift_iterations_state(X, b, iterations):
         bt = bt.expand(B)
     bsq = (bt.detach() ** 2).contiguous()
     with torch.no_grad():
-        st = _run_iterations(X.detach(), bsq, int(iterations), stacked=True)
+        st = _run_iterations(X.detach(), bsq, int(iterations), stacked=True, kind=kind)
         new_X = torch.gather(st.q, 1, st.inv.unsqueeze(2).expand(-1, -1, D)) if st.sparse else st.q
         if iterations == 0:
             new_X = new_X.clone()
     state = MeanShiftState()
     state.x, state.bsq, state.inv, state.iterations, state.new_X = st.x, bsq, st.inv, int(iterations), new_X
     state.iterates, state.rsums, state.norms = st.iterates_all, st.rsums_all, st.norms_all
+    state.kind = kind
+    if kind != K.KERNEL_GAUSSIAN and WANT_NEAREST:
+        LAST_NEAREST = None         # (nothing ran in a locality order: the caller's NMS selects for itself)
     return new_X, state
 
 
@@ -482,7 +511,7 @@ class _CentreRows(torch.autograd.Function):
         Qc = torch.gather(state.iterates, 2, rows.view(1, B, R, 1).expand(T + 1, B, R, D))          # (T+1,B,R,D)
         rc = torch.gather(state.rsums, 2, rows.view(1, B, R).expand(T, B, R))
         nc = torch.gather(state.norms, 2, rows.view(1, B, R).expand(T, B, R))
-        ctx.T = T
+        ctx.T, ctx.kind = T, state.kind
         ctx.has_inv = state.inv is not None
         ctx.save_for_backward(Qc, rc, nc, rows, state.x, state.bsq, *([state.inv] if state.inv is not None else []))
         return Qc[T].clone()
@@ -495,7 +524,7 @@ class _CentreRows(torch.autograd.Function):
         g = g.contiguous()
         ws = K.meanshift_rows_workspace(B, N, x.device)
         for t in reversed(range(ctx.T)):
-            g = K.meanshift_rows_bwd(g, Qc[t + 1], Qc[t], rc[t], nc[t], x, bsq, gX, ws)
+            g = K.meanshift_rows_bwd(g, Qc[t + 1], Qc[t], rc[t], nc[t], x, bsq, gX, ws, kind=ctx.kind)
         K.meanshift_rows_scatter_add(gX, rows, g)            # the first iterate is X itself
         if ctx.has_inv:
             inv = ctx.saved_tensors[6]
@@ -505,7 +534,10 @@ class _CentreRows(torch.autograd.Function):
 
 def centre_rows(X, state, ids):
     """Rows ``ids`` (B,R) of the final iterate of ``mean_shift_iterations_state(X, ...)`` with the gradient
-    path to X (R <= 64; ids may repeat; X as it was handed to ``mean_shift_iterations_state``: width 32, 64 or 128)."""
+    path to X (R <= 64; ids may repeat; X as it was handed to ``mean_shift_iterations_state``: width 32, 64 or 128).
+    The backward recomputes the kernel profile the state recorded."""
+    if state.kind != K.KERNEL_GAUSSIAN:
+        _require_fused_epanechnikov("centre_rows", X)
     if ids.shape[1] > 64:
         raise ValueError("centre_rows: at most 64 rows per batch item, got %d" % ids.shape[1])
     return _CentreRows.apply(X, state, ids)
@@ -541,11 +573,18 @@ class MeanShift:
         return new_X, center, bw, new_labels
 
     # -- the same in two stages, for callers that overlap shapes on two streams -------------
-    def shift_async(self, X, num_samples, quantile, iterations):
+    def shift_async(self, X, num_samples, quantile, iterations, kernel_type="gaussian"):
         """Stage 1 of ``mean_shift`` (bandwidth + iterations) WITHOUT any host synchronisation, so
         that it can be queued on a side stream while the host drives another shape's fitting
         stage.  Returns (new_X, bw, flag); flag (0-dim tensor) > 0 means the bandwidth selection met
-        massive ties and the caller must use ``mean_shift`` instead (checked in ``finish``)."""
+        massive ties and the caller must use ``mean_shift`` instead (checked in ``finish``).  ``kernel_type`` other
+        than "gaussian": the fused Epanechnikov kernel or a ValueError — the tensor expressions ``mean_shift_``
+        keeps for it would put N x N matrices on the side stream."""
+        if _kind_of(kernel_type) != K.KERNEL_GAUSSIAN:
+            _require_fused_epanechnikov("shift_async", X)
+            if kernel_width(X.shape[-1]) is None:
+                raise ValueError("shift_async: the fused Epanechnikov kernel (bf16x3 arithmetic) serves embedding "
+                                 "widths up to 128, got %d" % X.shape[-1])
         if num_samples < X.shape[0]:
             raise ValueError("shift_async needs num_samples >= N: the bandwidth then does not depend on the "
                              "shuffle, which is what lets ``finish`` draw it at the reference's place in "
@@ -553,7 +592,7 @@ class MeanShift:
         with torch.no_grad():
             bw, flag = self.compute_bandwidth(X, num_samples, quantile, defer_flags=True, defer_shuffle=True)
             bw = torch.clamp(bw, min=0.003)
-        new_X, _ = self.mean_shift_(X, b=bw, iterations=iterations)
+        new_X, _ = self.mean_shift_(X, b=bw, iterations=iterations, kernel_type=kernel_type)
         return new_X, bw, flag
 
     def finish(self, X, new_X, bw, flag=None):
