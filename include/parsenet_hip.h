@@ -812,6 +812,30 @@ int pn_trimesh_point_dist_f32(const float* points, const int* pt_off, const int*
                               int total_tiles, int waves, int prune, float* dist2, int* face,
                               unsigned long long* skipped, void* stream);
 
+/* ---- point normals from the cloud itself: k-NN PCA (csrc/normals.hip, arithmetic: csrc/normal_math.h) ----------
+ * The reference reads normals from its data files (its own estimate_normals call is commented out, src/utils.py:61);
+ * this produces them for a cloud that has none, for a RAGGED batch of S segments in one launch.
+ * pts (total,3) fp32, off (S+1) int32 row offsets, idx (total,k) int32: the LOCAL indices pn_knn3_ragged wrote (the
+ * point itself first; a segment with fewer than k points arrives padded with the point itself, and the padding
+ * entries count as copies of the point).  3 <= k <= 64.
+ * Per point, in fp64 on the fp32 coordinates, every sum in neighbour order: the mean of the k neighbours, the
+ * covariance of the differences to it (divided by k), its eigenvalues l0 <= l1 <= l2 by cyclic Jacobi (a fixed number
+ * of sweeps).  normals (total,3) fp32: the unit eigenvector of l0, rounded to fp32 once; viewpoints NULL: the
+ * component of largest magnitude is positive (the lowest axis on a tie); viewpoints (S,3) fp32: that normal, flipped
+ * iff n . (v_s - p) < 0 (fp64; a zero dot keeps it).  variation (total) fp32 or NULL: l0 / (l0 + l1 + l2);
+ * gap (total) fp32 or NULL: (l1 - l0) / l2, small where the normal is ill-defined (edges, corners, lines).
+ * l2 <= 1e-30 (coincident neighbours) or a segment of fewer than 3 points: normal (0,0,0), variation = gap = 0; no
+ * NaN for finite input.
+ * A workgroup owns pn_point_normals_tile() consecutive points of one segment: tile t starts at row tile_first[t] of
+ * segment tile_seg[t]; total_tiles = sum_s ceil(n_s / tile).  off and the tile tables are DEVICE arrays of int32.
+ * The result of a point depends on its neighbourhood alone: the same bits from run to run and for every batching.
+ * PN_ERR_ARG (before any launch) for k out of range, S < 0, total < 0 or a NULL required pointer; total == 0 or
+ * S == 0 returns 0 without a launch. */
+int pn_point_normals_tile(void);
+int pn_point_normals_f32(const float* pts, const int* off, int S, int total, const int32_t* idx, int k,
+                         const float* viewpoints, const int* tile_seg, const int* tile_first, int total_tiles,
+                         float* normals, float* variation, float* gap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

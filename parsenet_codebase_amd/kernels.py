@@ -109,6 +109,65 @@ def knn3_ragged(pts, off, max_n, k, f64=False, want_dist=False):
     return (idx, dist) if want_dist else idx
 
 
+NORMALS_MIN_K, NORMALS_MAX_K = 3, 64
+
+
+def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
+    """k-NN PCA normals of the points of a ragged batch (csrc/normals.hip, arithmetic csrc/normal_math.h): the unit
+    eigenvector of the smallest eigenvalue of the covariance of every point's k neighbours.
+    pts (total,3) fp32 and idx (total,k) int32 on the GPU, idx the LOCAL indices ``knn3_ragged`` returned; off (S+1):
+    HOST integers (the caller built them) — they are checked here (ascending from 0 to total) and uploaded with the
+    tile table in one stream-ordered copy.  viewpoints (S,3) fp32 on the GPU or None.
+    Returns normals (total,3) fp32 — canonical sign (largest component positive) without viewpoints, else flipped
+    towards the segment's viewpoint — and, with ``want_scalars``, (normals, variation (total), gap (total)).
+    A neighbourhood of coincident points and a segment of fewer than 3 points give zero normals and scalars."""
+    import numpy as np
+    require_cuda(pts, idx, viewpoints)
+    if torch.is_tensor(off):
+        if off.is_cuda:
+            raise TypeError("point_normals: off must be host integers (a list, an array or a CPU tensor)")
+        off = off.numpy()
+    pts = _f32c(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("point_normals expects (total,3) points, got %s" % (tuple(pts.shape),))
+    k = int(k)
+    if not NORMALS_MIN_K <= k <= NORMALS_MAX_K:
+        raise ValueError("point_normals: k must be %d .. %d, got %d" % (NORMALS_MIN_K, NORMALS_MAX_K, k))
+    total = pts.shape[0]
+    if idx.dtype != torch.int32:
+        raise TypeError("idx must be int32, got %s" % idx.dtype)
+    if tuple(idx.shape) != (total, k):
+        raise ValueError("point_normals expects (%d,%d) neighbour indices, got %s" % (total, k, tuple(idx.shape)))
+    off = np.asarray(off, np.int64).reshape(-1)
+    S = off.shape[0] - 1
+    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+        raise ValueError("point_normals: off must ascend from 0 to %d" % total)
+    if total * max(k, 3) >= 2 ** 31:
+        raise ValueError("point_normals: int32 offsets")
+    dev = pts.device
+    if viewpoints is not None:
+        viewpoints = _f32c(viewpoints, "viewpoints")
+        if tuple(viewpoints.shape) != (S, 3):
+            raise ValueError("point_normals expects (%d,3) viewpoints, got %s" % (S, tuple(viewpoints.shape)))
+    normals = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    variation = torch.empty(total, dtype=torch.float32, device=dev) if want_scalars else None
+    gap = torch.empty(total, dtype=torch.float32, device=dev) if want_scalars else None
+    if total > 0:
+        lib = _lib.load()
+        tile = lib.pn_point_normals_tile()
+        tiles = (np.diff(off) + tile - 1) // tile
+        ntile = int(tiles.sum())
+        tile_seg = np.repeat(np.arange(S), tiles)
+        tile_first = off[tile_seg] + (np.arange(ntile) - np.repeat(np.cumsum(tiles) - tiles, tiles)) * tile
+        table = _lib.h2d(np.concatenate([off, tile_seg, tile_first]).astype(np.int32), dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_point_normals_f32(ptr(pts), ptr(table), S, total, ptr(idx.contiguous()), k, ptr(viewpoints),
+                                          ptr(table[S + 1:]), ptr(table[S + 1 + ntile:]), ntile, ptr(normals),
+                                          ptr(variation), ptr(gap), current_stream(dev))
+        check(rc, "pn_point_normals_f32")
+    return (normals, variation, gap) if want_scalars else normals
+
+
 def _i64c(t, name):
     if t.dtype != torch.int64:
         raise TypeError("%s must be int64, got %s" % (name, t.dtype))
