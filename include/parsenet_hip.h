@@ -836,6 +836,27 @@ int pn_point_normals_f32(const float* pts, const int* off, int S, int total, con
                          const float* viewpoints, const int* tile_seg, const int* tile_first, int total_tiles,
                          float* normals, float* variation, float* gap, void* stream);
 
+/* ---- consistent normal orientation without a viewpoint (csrc/orient.hip, definition: csrc/orient_math.h) --------
+ * Signs are propagated along the minimum spanning forest of the k-NN graph under the weight 1 - |n_i . n_j| (Hoppe
+ * et al. 1992), for a RAGGED batch of S segments in one launch, one workgroup per segment, no workspace.
+ * pts (total,3) fp32 (only z is read: the seed rule), off (S+1) DEVICE int32 row offsets, idx (total,k) int32: the
+ * LOCAL indices pn_knn3_ragged wrote, 1 <= k <= 64; normals_in (total,3) fp32, from anywhere.
+ * Entries: one per (point i, slot s), e = i k + s, j = idx[i][s]; an entry with j == i (self and padding) or j outside
+ * the segment is dropped; an entry is incident to i and to j.  dot = (nx_i nx_j + ny_i ny_j) + nz_i nz_j in fp64,
+ * w = (float) max(0, 1 - |dot|), neg = dot < 0 (a zero normal: w = 1, neg = false).  Entries are ordered by the key
+ * (bits of w) << 32 | e, a strict order, so the minimum spanning forest is unique.  Along every forest edge
+ * flip(j) = flip(i) XOR neg.  The seed of a connected component is its vertex of largest fp32 z (the lowest index on
+ * equal z); the component's bit makes the seed's oriented n_z >= 0 (a seed with n_z == 0 keeps flip = 0).
+ * normals_out (total,3): the input normal, bit-identical or with every sign bit inverted; it must not be normals_in.
+ * flip (total) int32 0/1 or NULL; seed (total) int32 or NULL: the local index of the seed of the point's component.
+ * All outputs are functions of the input alone: the same bits from run to run and for every batching.
+ * A segment of more than pn_orient_normals_max_points() points is not truncated: its normals come out NaN, its flip
+ * and seed -1.  PN_ERR_ARG (before any launch) for k out of range, S < 0, total < 0 or a NULL required pointer;
+ * total == 0 or S == 0 returns 0 without a launch. */
+int pn_orient_normals_max_points(void);
+int pn_orient_normals_f32(const float* pts, const int* off, int S, int total, const int32_t* idx, int k,
+                          const float* normals_in, float* normals_out, int32_t* flip, int32_t* seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

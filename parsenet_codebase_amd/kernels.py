@@ -168,6 +168,63 @@ def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
     return (normals, variation, gap) if want_scalars else normals
 
 
+ORIENT_MIN_K, ORIENT_MAX_K = 1, 64
+
+
+def orient_normals(pts, off, idx, k, normals, want_flags=False):
+    """Consistent orientation of the normals of a ragged batch without a viewpoint (csrc/orient.hip, definition
+    csrc/orient_math.h): signs propagated along the minimum spanning forest of the k-NN graph under 1 - |n_i . n_j|,
+    the topmost point of every connected component looking up.
+    pts (total,3) fp32, idx (total,k) int32 — the LOCAL indices ``knn3_ragged`` returned — and normals (total,3) fp32
+    on the GPU; off (S+1): HOST integers, checked here (ascending from 0 to total, no segment above
+    ``pn_orient_normals_max_points()``: ValueError) and uploaded in one stream-ordered copy.
+    Returns the oriented normals (total,3) — every row the input row, bit-identical or negated — and, with
+    ``want_flags``, (normals, flip (total) int32 0/1, seed (total) int32: the local index of the component's seed).
+    One launch, no host synchronisation; the same bits from run to run and for every batching."""
+    import numpy as np
+    require_cuda(pts, idx, normals)
+    if torch.is_tensor(off):
+        if off.is_cuda:
+            raise TypeError("orient_normals: off must be host integers (a list, an array or a CPU tensor)")
+        off = off.numpy()
+    pts = _f32c(pts, "pts")
+    normals = _f32c(normals, "normals")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("orient_normals expects (total,3) points, got %s" % (tuple(pts.shape),))
+    total = pts.shape[0]
+    if tuple(normals.shape) != (total, 3):
+        raise ValueError("orient_normals expects (%d,3) normals, got %s" % (total, tuple(normals.shape)))
+    k = int(k)
+    if not ORIENT_MIN_K <= k <= ORIENT_MAX_K:
+        raise ValueError("orient_normals: k must be %d .. %d, got %d" % (ORIENT_MIN_K, ORIENT_MAX_K, k))
+    if idx.dtype != torch.int32:
+        raise TypeError("idx must be int32, got %s" % idx.dtype)
+    if tuple(idx.shape) != (total, k):
+        raise ValueError("orient_normals expects (%d,%d) neighbour indices, got %s" % (total, k, tuple(idx.shape)))
+    off = np.asarray(off, np.int64).reshape(-1)
+    S = off.shape[0] - 1
+    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+        raise ValueError("orient_normals: off must ascend from 0 to %d" % total)
+    if total * max(k, 3) >= 2 ** 31:
+        raise ValueError("orient_normals: int32 offsets")
+    dev = pts.device
+    out = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    flip = torch.empty(total, dtype=torch.int32, device=dev) if want_flags else None
+    seed = torch.empty(total, dtype=torch.int32, device=dev) if want_flags else None
+    if total > 0:
+        lib = _lib.load()
+        limit = lib.pn_orient_normals_max_points()
+        if int(np.diff(off).max()) > limit:
+            raise ValueError("orient_normals: a cloud of %d points; one workgroup orients at most %d points"
+                             % (int(np.diff(off).max()), limit))
+        table = _lib.h2d(off.astype(np.int32), dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_orient_normals_f32(ptr(pts), ptr(table), S, total, ptr(idx.contiguous()), k, ptr(normals),
+                                           ptr(out), ptr(flip), ptr(seed), current_stream(dev))
+        check(rc, "pn_orient_normals_f32")
+    return (out, flip, seed) if want_flags else out
+
+
 def _i64c(t, name):
     if t.dtype != torch.int64:
         raise TypeError("%s must be int64, got %s" % (name, t.dtype))

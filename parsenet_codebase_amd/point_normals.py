@@ -1,4 +1,4 @@
-"""Point normals from the cloud itself: k-NN PCA on the GPU.
+"""Point normals from the cloud itself: k-NN PCA on the GPU, and their consistent orientation.
 
 Every path that starts from a raw cloud needs per-point normals — the cylinder and cone fits, the 6-channel network,
 the evaluation entry points — and the reference only ever reads them from its data files (its own estimate_normals
@@ -8,7 +8,13 @@ difference-form neighbours, exactly ordered) and one launch of csrc/normals.hip,
 
 Without a viewpoint the sign is canonical (the component of largest magnitude is positive), NOT consistent over a
 closed shape: that serves the cylinder fit and every other sign-invariant use.  The cone fit's axis test and the
-network trained on outward normals need oriented normals, i.e. a viewpoint the whole shape is seen from."""
+network trained on outward normals need oriented normals.  A viewpoint the whole shape is seen from gives them for a
+scan from one side; for a closed shape, which no single viewpoint sees, ``orient_normals`` (or
+``estimate_normals(..., orient="mst")``) propagates the signs along the minimum spanning forest of the k-NN graph
+under the weight 1 - |n_i . n_j| (Hoppe et al. 1992) and lets the topmost point of every connected component look up:
+one more launch (csrc/orient.hip, definition csrc/orient_math.h), outputs exactly defined.  The method's known
+weakness stays: the tree can cross a sharp crease or a thin wall with the wrong sign, and an open patch gets a
+consistent but arbitrary side."""
 import numpy as np
 import torch
 
@@ -39,7 +45,58 @@ def _viewpoints(viewpoint, S, device):
     return viewpoint.to(device).contiguous()
 
 
-def estimate_normals(points, k=16, viewpoint=None, return_scalars=False):
+def _clouds(points, who, what="points"):
+    """(N,3), (B,N,3) or a list of (N_b,3) fp32 tensors on the GPU -> (layout, sizes, flat (total,3)); layout is
+    "single", "list" or the shape (B, N) of a batch."""
+    if isinstance(points, (list, tuple)):
+        clouds = list(points)
+        if not clouds:
+            raise ValueError("%s: an empty list of clouds" % who)
+        if not all(torch.is_tensor(c) for c in clouds):
+            raise TypeError("%s: a list of clouds holds tensors" % who)
+        layout = "list"
+    elif torch.is_tensor(points):
+        clouds = [points]
+        layout = "single" if points.dim() == 2 else "batch"
+    else:
+        raise TypeError("%s: %s must be a tensor or a list of tensors" % (who, what))
+    _lib.require_cuda(*clouds)
+    for c in clouds:
+        if c.dtype != torch.float32:
+            raise ValueError("%s: %s must be float32, got %s" % (who, what, c.dtype))
+        if c.dim() != (3 if layout == "batch" else 2) or c.shape[-1] != 3:
+            raise ValueError("%s: %s must be (N,3), (B,N,3) or a list of (N,3), got %s" % (who, what, tuple(c.shape)))
+    if layout == "batch":
+        B, N = points.shape[:2]
+        return (B, N), [N] * B, points.reshape(B * N, 3)
+    return layout, [c.shape[0] for c in clouds], clouds[0] if len(clouds) == 1 else torch.cat(clouds)
+
+
+def _check_sizes(sizes, who):
+    if sizes and max(sizes) > KNN3_MAX_POINTS:
+        raise ValueError("%s: a cloud of %d points; the neighbour search takes at most %d points per cloud"
+                         % (who, max(sizes), KNN3_MAX_POINTS))
+
+
+def _neighbours(flat, sizes, k):
+    """One knn3_ragged call over the ragged batch: (host offsets (S+1) int64, idx (total,k) int32)."""
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if int(off[-1]) == 0:
+        return off, torch.empty((0, k), dtype=torch.int32, device=flat.device)
+    return off, K.knn3_ragged(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), k)
+
+
+def _shaped(out, layout, sizes):
+    """(total,3) and (total,) results back in the layout of the input."""
+    if isinstance(layout, tuple):
+        B, N = layout
+        return tuple(o.reshape(B, N, 3) if o.dim() == 2 else o.reshape(B, N) for o in out)
+    if layout == "list":
+        return tuple(list(torch.split(o, sizes)) for o in out)
+    return tuple(out)
+
+
+def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None):
     """Normals of a cloud that has none.
 
     points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
@@ -47,55 +104,57 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False):
        (the missing neighbours count as copies of the point); fewer than 3 points give zero normals.
     viewpoint: None — canonical sign, the component of largest magnitude positive —, or (3,), (B,3) or a list of (3,)
        tensors: the normal of point p is flipped iff n . (viewpoint - p) < 0.
+    orient: None, or "mst": the canonical-sign normals are oriented consistently over every cloud as ``orient_normals``
+       does, on the neighbours this call has already found — one more launch.  Not together with a viewpoint, which
+       already signs every point.
     Returns the normals in the layout of ``points``; with ``return_scalars`` a tuple (normals, variation, gap):
     variation = l0 / (l0 + l1 + l2) and gap = (l1 - l0) / l2 of the covariance's eigenvalues l0 <= l1 <= l2, one per
     point ((N,), (B,N) or a list).  A point whose neighbours coincide gets the zero normal and zero scalars.
     No host synchronisation and no download: the sizes come from the shapes."""
-    if isinstance(points, (list, tuple)):
-        clouds = list(points)
-        if not clouds:
-            raise ValueError("estimate_normals: an empty list of clouds")
-        if not all(torch.is_tensor(c) for c in clouds):
-            raise TypeError("estimate_normals: a list of clouds holds tensors")
-        layout = "list"
-    elif torch.is_tensor(points):
-        clouds = [points]
-        layout = "single" if points.dim() == 2 else "batch"
-    else:
-        raise TypeError("estimate_normals: points must be a tensor or a list of tensors")
-    _lib.require_cuda(*clouds)
-    for c in clouds:
-        if c.dtype != torch.float32:
-            raise ValueError("estimate_normals: points must be float32, got %s" % c.dtype)
-        if c.dim() != (3 if layout == "batch" else 2) or c.shape[-1] != 3:
-            raise ValueError("estimate_normals: points must be (N,3), (B,N,3) or a list of (N,3), got %s"
-                             % (tuple(c.shape),))
+    if orient not in (None, "mst"):
+        raise ValueError("estimate_normals: orient must be None or \"mst\", got %r" % (orient,))
+    if orient is not None and viewpoint is not None:
+        raise ValueError("estimate_normals: orient=\"mst\" together with a viewpoint (a viewpoint already signs every "
+                         "point)")
+    layout, sizes, flat = _clouds(points, "estimate_normals")
     k = int(k)
     if not K.NORMALS_MIN_K <= k <= K.NORMALS_MAX_K:
         raise ValueError("estimate_normals: k must be %d .. %d, got %d" % (K.NORMALS_MIN_K, K.NORMALS_MAX_K, k))
-    if layout == "batch":
-        B, N = points.shape[:2]
-        sizes = [N] * B
-        flat = points.reshape(B * N, 3)
-    else:
-        sizes = [c.shape[0] for c in clouds]
-        flat = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
-    if sizes and max(sizes) > KNN3_MAX_POINTS:
-        raise ValueError("estimate_normals: a cloud of %d points; the neighbour search takes at most %d points per "
-                         "cloud" % (max(sizes), KNN3_MAX_POINTS))
-    S = len(sizes)
-    dev = flat.device
-    view = _viewpoints(viewpoint, S, dev)
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    total = int(off[-1])
-    if total == 0:
-        idx = torch.empty((0, k), dtype=torch.int32, device=dev)
-    else:
-        idx = K.knn3_ragged(flat, _lib.h2d(off.astype(np.int32), dev), max(sizes), k)
+    _check_sizes(sizes, "estimate_normals")
+    view = _viewpoints(viewpoint, len(sizes), flat.device)
+    off, idx = _neighbours(flat, sizes, k)
     out = K.point_normals(flat, off, idx, k, viewpoints=view, want_scalars=return_scalars)
     out = out if return_scalars else (out,)
-    if layout == "batch":
-        out = (out[0].reshape(B, N, 3),) + tuple(o.reshape(B, N) for o in out[1:])
-    elif layout == "list":
-        out = tuple(list(torch.split(o, sizes)) for o in out)
+    if orient == "mst":
+        out = (K.orient_normals(flat, off, idx, k, out[0]),) + tuple(out[1:])
+    out = _shaped(out, layout, sizes)
     return tuple(out) if return_scalars else out[0]
+
+
+def orient_normals(points, normals, k=16, return_flags=False):
+    """Consistent orientation of normals without a viewpoint: spanning-tree propagation (Hoppe et al. 1992).
+
+    points, normals: (N,3) or (B,N,3) fp32 on the GPU, or lists of (N_b,3) tensors, in the same layout; the normals may
+       come from anywhere (a zero normal stays zero).
+    k: neighbours per point in the graph the signs travel along, the point itself included, 1 .. 64.
+    Per cloud: the minimum spanning forest of the k-NN graph under the weight 1 - |n_i . n_j| (csrc/orient_math.h fixes
+    the arithmetic and a strict order on the edges, so the forest is unique); along every tree edge a normal is flipped
+    iff it disagrees with its neighbour; in every connected component of the graph the point with the largest z (the
+    lowest index on equal z) ends with n_z >= 0 — on a closed surface the outward normal of the topmost point is +z.
+    Returns the oriented normals in the layout of ``normals`` — each the input normal or its negation, exactly; with
+    ``return_flags`` a tuple (normals, flip, seed): flip 0/1 and the in-cloud index of the component's seed, int32,
+    (N,), (B,N) or a list.  One ``knn3_ragged`` call and one launch of csrc/orient.hip, no host synchronisation.
+    Limits: the tree can cross a sharp crease or a thin wall with the wrong sign; an open patch gets a consistent but
+    arbitrary side; a cloud above ``pn_orient_normals_max_points()`` (10 240) points is a ValueError."""
+    layout, sizes, flat = _clouds(points, "orient_normals")
+    n_layout, n_sizes, n_flat = _clouds(normals, "orient_normals", "normals")
+    if (n_layout, n_sizes) != (layout, sizes):
+        raise ValueError("orient_normals: points and normals must have the same layout and sizes")
+    k = int(k)
+    if not K.ORIENT_MIN_K <= k <= K.ORIENT_MAX_K:
+        raise ValueError("orient_normals: k must be %d .. %d, got %d" % (K.ORIENT_MIN_K, K.ORIENT_MAX_K, k))
+    _check_sizes(sizes, "orient_normals")
+    off, idx = _neighbours(flat, sizes, k)
+    out = K.orient_normals(flat, off, idx, k, n_flat, want_flags=return_flags)
+    out = _shaped(out if return_flags else (out,), layout, sizes)
+    return tuple(out) if return_flags else out[0]
