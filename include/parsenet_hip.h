@@ -857,6 +857,24 @@ int pn_orient_normals_max_points(void);
 int pn_orient_normals_f32(const float* pts, const int* off, int S, int total, const int32_t* idx, int k,
                           const float* normals_in, float* normals_out, int32_t* flip, int32_t* seed, void* stream);
 
+/* ---- exact neighbours of 3-D points on clouds of any size: uniform-grid search (csrc/knn3_grid.hip, definition:
+ * csrc/knn3_grid_math.h) --------------------------------------------------------------------------------------------
+ * The results of pn_knn3_ragged's fp32 mode, bit for bit, at cost O(n k) and without its limit on the segment size.
+ * pts (total,3) fp32, off (S+1) DEVICE int32 row offsets, max_n >= the largest segment (kept for symmetry with
+ * pn_knn3_ragged: nothing is sized by it).  idx (total,k) int32 LOCAL to the segment: the k smallest under
+ * d(i,j) = ((x_i-x_j)^2 + (y_i-y_j)^2) + (z_i-z_j)^2, every operation rounded once in fp32, no fma, ordered by (d, j)
+ * ascending — the point itself (or a coincident point of smaller index) first; a segment with fewer than k points is
+ * padded with the point itself.  dist (total,k) fp32 or NULL: (float) sqrt((double) d).  1 <= k <= 64, any segment
+ * size, total * k < 2^31.  A segment that holds a non-finite coordinate: every row the point itself k times, dist NaN.
+ * Five stream-ordered launches (bounding boxes, cells and histogram, scan, scatter into cell order, search), no host
+ * synchronisation; workspace of pn_knn3_grid_workspace_bytes(total, S) bytes, linear in total.  All outputs are
+ * functions of the input alone: the same bits from run to run and for every batching.
+ * PN_ERR_ARG (before any launch) for k out of range, S < 0, total < 0, a NULL required pointer or a workspace that is
+ * too small; total == 0 or S == 0 returns 0 without a launch. */
+long long pn_knn3_grid_workspace_bytes(long long total, int S);
+int pn_knn3_grid_f32(const float* pts, const int* off, int S, int total, int max_n, int k, int32_t* idx, float* dist,
+                     void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

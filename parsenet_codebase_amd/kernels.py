@@ -109,6 +109,39 @@ def knn3_ragged(pts, off, max_n, k, f64=False, want_dist=False):
     return (idx, dist) if want_dist else idx
 
 
+def knn3_grid(pts, off, max_n, k, want_dist=False):
+    """``knn3_ragged``'s fp32 neighbours, bit for bit, by a uniform-grid search (csrc/knn3_grid.hip, definition
+    csrc/knn3_grid_math.h): cost O(n k) and no limit on the size of a segment.  pts (total,3) fp32, off (S+1) int32
+    device offsets, max_n >= the largest segment (a host integer).  Returns idx (total,k) int32 LOCAL to the segment —
+    nearest first, the point itself first, equal distances to the smaller index, a segment shorter than k padded with
+    the point itself — and, with ``want_dist``, their fp32 distances.  1 <= k <= 64, total * k < 2^31.  A segment that
+    holds a non-finite coordinate gets the point itself k times and NaN distances.  Five stream-ordered launches on a
+    workspace linear in total, no host synchronisation."""
+    require_cuda(pts, off)
+    pts = _f32c(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("knn3_grid expects (total,3) points, got %s" % (tuple(pts.shape),))
+    if off.dtype != torch.int32:
+        raise TypeError("off must be int32")
+    k = int(k)
+    S = off.numel() - 1
+    total = pts.shape[0]
+    if total * max(k, 1) >= 2 ** 31:
+        raise ValueError("knn3_grid: total * k = %d (below 2^31)" % (total * k))
+    idx = torch.empty((total, k), dtype=torch.int32, device=pts.device)
+    dist = torch.empty((total, k), dtype=torch.float32, device=pts.device) if want_dist else None
+    if total == 0 or S <= 0:
+        return (idx, dist) if want_dist else idx
+    lib = _lib.load()
+    wsz = lib.pn_knn3_grid_workspace_bytes(total, S)
+    ws = torch.empty(wsz, dtype=torch.uint8, device=pts.device)
+    with _lib.on_device(pts.device):
+        rc = lib.pn_knn3_grid_f32(ptr(pts), ptr(off.contiguous()), S, total, int(max_n), k, ptr(idx), ptr(dist), ptr(ws),
+                                  wsz, current_stream(pts.device))
+    check(rc, "pn_knn3_grid_f32")
+    return (idx, dist) if want_dist else idx
+
+
 NORMALS_MIN_K, NORMALS_MAX_K = 3, 64
 
 

@@ -72,18 +72,24 @@ def _clouds(points, who, what="points"):
     return layout, [c.shape[0] for c in clouds], clouds[0] if len(clouds) == 1 else torch.cat(clouds)
 
 
-def _check_sizes(sizes, who):
-    if sizes and max(sizes) > KNN3_MAX_POINTS:
-        raise ValueError("%s: a cloud of %d points; the neighbour search takes at most %d points per cloud"
-                         % (who, max(sizes), KNN3_MAX_POINTS))
+def _search(search, sizes, who):
+    """The neighbour search of a call: ``search`` checked and resolved to "brute" (knn3_ragged) or "grid" (knn3_grid)."""
+    if search not in (None, "grid", "auto"):
+        raise ValueError("%s: search must be None, \"grid\" or \"auto\", got %r" % (who, search))
+    big = bool(sizes) and max(sizes) > KNN3_MAX_POINTS
+    if search is None and big:
+        raise ValueError("%s: a cloud of %d points; the brute-force neighbour search takes at most %d points per cloud "
+                         "(search=\"grid\" lifts the limit)" % (who, max(sizes), KNN3_MAX_POINTS))
+    return "grid" if search == "grid" or (search == "auto" and big) else "brute"
 
 
-def _neighbours(flat, sizes, k):
-    """One knn3_ragged call over the ragged batch: (host offsets (S+1) int64, idx (total,k) int32)."""
+def _neighbours(flat, sizes, k, search="brute"):
+    """One neighbour search over the ragged batch: (host offsets (S+1) int64, idx (total,k) int32)."""
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     if int(off[-1]) == 0:
         return off, torch.empty((0, k), dtype=torch.int32, device=flat.device)
-    return off, K.knn3_ragged(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), k)
+    knn3 = K.knn3_grid if search == "grid" else K.knn3_ragged
+    return off, knn3(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), k)
 
 
 def _shaped(out, layout, sizes):
@@ -96,7 +102,7 @@ def _shaped(out, layout, sizes):
     return tuple(out)
 
 
-def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None):
+def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None, search=None):
     """Normals of a cloud that has none.
 
     points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
@@ -106,7 +112,12 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
        tensors: the normal of point p is flipped iff n . (viewpoint - p) < 0.
     orient: None, or "mst": the canonical-sign normals are oriented consistently over every cloud as ``orient_normals``
        does, on the neighbours this call has already found — one more launch.  Not together with a viewpoint, which
-       already signs every point.
+       already signs every point.  Its own limit stays whatever the search: a cloud above
+       ``pn_orient_normals_max_points()`` (10 240) points is a ValueError.
+    search: the neighbour search.  None — the brute-force kernel (csrc/knn3.hip), at most 10 240 points per cloud;
+       "grid" — the uniform-grid search (csrc/knn3_grid.hip), the same neighbours bit for bit on clouds of any size;
+       "auto" — brute force when every cloud has at most 10 240 points, the grid otherwise.  The result does not depend
+       on the choice.
     Returns the normals in the layout of ``points``; with ``return_scalars`` a tuple (normals, variation, gap):
     variation = l0 / (l0 + l1 + l2) and gap = (l1 - l0) / l2 of the covariance's eigenvalues l0 <= l1 <= l2, one per
     point ((N,), (B,N) or a list).  A point whose neighbours coincide gets the zero normal and zero scalars.
@@ -120,9 +131,9 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
     k = int(k)
     if not K.NORMALS_MIN_K <= k <= K.NORMALS_MAX_K:
         raise ValueError("estimate_normals: k must be %d .. %d, got %d" % (K.NORMALS_MIN_K, K.NORMALS_MAX_K, k))
-    _check_sizes(sizes, "estimate_normals")
+    search = _search(search, sizes, "estimate_normals")
     view = _viewpoints(viewpoint, len(sizes), flat.device)
-    off, idx = _neighbours(flat, sizes, k)
+    off, idx = _neighbours(flat, sizes, k, search)
     out = K.point_normals(flat, off, idx, k, viewpoints=view, want_scalars=return_scalars)
     out = out if return_scalars else (out,)
     if orient == "mst":
@@ -131,7 +142,7 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
     return tuple(out) if return_scalars else out[0]
 
 
-def orient_normals(points, normals, k=16, return_flags=False):
+def orient_normals(points, normals, k=16, return_flags=False, search=None):
     """Consistent orientation of normals without a viewpoint: spanning-tree propagation (Hoppe et al. 1992).
 
     points, normals: (N,3) or (B,N,3) fp32 on the GPU, or lists of (N_b,3) tensors, in the same layout; the normals may
@@ -143,7 +154,8 @@ def orient_normals(points, normals, k=16, return_flags=False):
     lowest index on equal z) ends with n_z >= 0 — on a closed surface the outward normal of the topmost point is +z.
     Returns the oriented normals in the layout of ``normals`` — each the input normal or its negation, exactly; with
     ``return_flags`` a tuple (normals, flip, seed): flip 0/1 and the in-cloud index of the component's seed, int32,
-    (N,), (B,N) or a list.  One ``knn3_ragged`` call and one launch of csrc/orient.hip, no host synchronisation.
+    (N,), (B,N) or a list.  One neighbour search and one launch of csrc/orient.hip, no host synchronisation.
+    search: None, "grid" or "auto" as in ``estimate_normals`` — the same neighbours, hence the same result.
     Limits: the tree can cross a sharp crease or a thin wall with the wrong sign; an open patch gets a consistent but
     arbitrary side; a cloud above ``pn_orient_normals_max_points()`` (10 240) points is a ValueError."""
     layout, sizes, flat = _clouds(points, "orient_normals")
@@ -153,8 +165,8 @@ def orient_normals(points, normals, k=16, return_flags=False):
     k = int(k)
     if not K.ORIENT_MIN_K <= k <= K.ORIENT_MAX_K:
         raise ValueError("orient_normals: k must be %d .. %d, got %d" % (K.ORIENT_MIN_K, K.ORIENT_MAX_K, k))
-    _check_sizes(sizes, "orient_normals")
-    off, idx = _neighbours(flat, sizes, k)
+    search = _search(search, sizes, "orient_normals")
+    off, idx = _neighbours(flat, sizes, k, search)
     out = K.orient_normals(flat, off, idx, k, n_flat, want_flags=return_flags)
     out = _shaped(out if return_flags else (out,), layout, sizes)
     return tuple(out) if return_flags else out[0]
