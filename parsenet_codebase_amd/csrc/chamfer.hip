@@ -607,10 +607,15 @@ __global__ __launch_bounds__(256) void pn_chamfer_ragged_bwd_kernel(
   if (on) {
     const float* p = pred + (size_t)(a0 + il) * 3;
     px = p[0], py = p[1], pz = p[2];
-    const float* q = gt + (size_t)(b0 + (int)argA[a0 + il]) * 3;
-    ax = (px - q[0]) * ga;
-    ay = (py - q[1]) * ga;
-    az = (pz - q[2]) * ga;
+    const int64_t ja = argA[a0 + il];
+    if (ja >= 0 && ja < nB) {
+      const float* q = gt + (size_t)(b0 + (int)ja) * 3;
+      ax = (px - q[0]) * ga;
+      ay = (py - q[1]) * ga;
+      az = (pz - q[2]) * ga;
+    } else {   // the empty key of a non-finite prediction names no target: no address is formed, the row is NaN
+      ax = ay = az = __builtin_nanf("");
+    }
   }
   // four chunks of 64 targets per trip: their index loads (and the coordinates of the hits) are in flight
   // together — one chunk per trip waited a memory latency per 64 targets (116 us for the step's spline segments)
