@@ -875,6 +875,28 @@ long long pn_knn3_grid_workspace_bytes(long long total, int S);
 int pn_knn3_grid_f32(const float* pts, const int* off, int S, int total, int max_n, int k, int32_t* idx, float* dist,
                      void* ws, long long ws_bytes, void* stream);
 
+/* ---- consistent normal orientation on clouds of any size: the global-memory engine (csrc/orient_global.hip, steps
+ * and schedule: csrc/orient_global_math.h, definition: csrc/orient_math.h) -------------------------------------------
+ * The definition, the arguments and the outputs of pn_orient_normals_f32, bit for bit, with no limit on the points of
+ * a segment: the Boruvka state (a packed parent word and a 64-bit slot per point, the pending hooks) lives in a
+ * workspace of pn_orient_normals_global_workspace_bytes(total, S) bytes, linear in total, and every step runs over
+ * many workgroups.  max_n >= the largest segment (a host integer): it alone fixes the schedule —
+ * ceil(log2 max_n) + 1 rounds of one offer launch (64-bit integer atomic minima), one hook launch and
+ * ceil(log_64 max_n) compress launches (every vertex walks up to 64 parents), between one init launch and two tail
+ * launches; pn_orient_normals_global_launches(max_n) is that number of kernel launches (two memsets come on top) and
+ * needs no GPU.  All of it is stream-ordered: no host synchronisation, no cooperative launch, no waiting between
+ * workgroups; once no component finds an entry the remaining launches exit at a device flag.
+ * A point that no valid segment of off holds gets NaN normals, flip and seed -1.  A max_n below the largest segment
+ * can end the rounds early (a wrong forest, never an access outside the buffers).
+ * PN_ERR_ARG (before any launch) for k out of range, S < 0, total < 0, max_n < 0, total * k >= 2^31, a NULL required
+ * pointer (the workspace included), normals_out == normals_in or a workspace that is too small; total == 0 or S == 0
+ * returns 0 without a launch. */
+long long pn_orient_normals_global_workspace_bytes(long long total, int S);
+int pn_orient_normals_global_launches(int max_n);
+int pn_orient_normals_global_f32(const float* pts, const int* off, int S, int total, int max_n, const int32_t* idx,
+                                 int k, const float* normals_in, float* normals_out, int32_t* flip, int32_t* seed,
+                                 void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,37 @@ def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
 ORIENT_MIN_K, ORIENT_MAX_K = 1, 64
 
 
+def _orient_args(who, pts, off, idx, k, normals):
+    """The checks ``orient_normals`` and ``orient_normals_global`` share -> (pts, normals, host offsets int64, S, k)."""
+    import numpy as np
+    require_cuda(pts, idx, normals)
+    if torch.is_tensor(off):
+        if off.is_cuda:
+            raise TypeError("%s: off must be host integers (a list, an array or a CPU tensor)" % who)
+        off = off.numpy()
+    pts = _f32c(pts, "pts")
+    normals = _f32c(normals, "normals")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("%s expects (total,3) points, got %s" % (who, tuple(pts.shape),))
+    total = pts.shape[0]
+    if tuple(normals.shape) != (total, 3):
+        raise ValueError("%s expects (%d,3) normals, got %s" % (who, total, tuple(normals.shape)))
+    k = int(k)
+    if not ORIENT_MIN_K <= k <= ORIENT_MAX_K:
+        raise ValueError("%s: k must be %d .. %d, got %d" % (who, ORIENT_MIN_K, ORIENT_MAX_K, k))
+    if idx.dtype != torch.int32:
+        raise TypeError("idx must be int32, got %s" % idx.dtype)
+    if tuple(idx.shape) != (total, k):
+        raise ValueError("%s expects (%d,%d) neighbour indices, got %s" % (who, total, k, tuple(idx.shape)))
+    off = np.asarray(off, np.int64).reshape(-1)
+    S = off.shape[0] - 1
+    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+        raise ValueError("%s: off must ascend from 0 to %d" % (who, total))
+    if total * max(k, 3) >= 2 ** 31:
+        raise ValueError("%s: int32 offsets" % who)
+    return pts, normals, off, S, k
+
+
 def orient_normals(pts, off, idx, k, normals, want_flags=False):
     """Consistent orientation of the normals of a ragged batch without a viewpoint (csrc/orient.hip, definition
     csrc/orient_math.h): signs propagated along the minimum spanning forest of the k-NN graph under 1 - |n_i . n_j|,
@@ -213,33 +244,11 @@ def orient_normals(pts, off, idx, k, normals, want_flags=False):
     ``pn_orient_normals_max_points()``: ValueError) and uploaded in one stream-ordered copy.
     Returns the oriented normals (total,3) — every row the input row, bit-identical or negated — and, with
     ``want_flags``, (normals, flip (total) int32 0/1, seed (total) int32: the local index of the component's seed).
-    One launch, no host synchronisation; the same bits from run to run and for every batching."""
+    One launch, no host synchronisation; the same bits from run to run and for every batching.
+    ``orient_normals_global`` computes the same on segments of any size."""
     import numpy as np
-    require_cuda(pts, idx, normals)
-    if torch.is_tensor(off):
-        if off.is_cuda:
-            raise TypeError("orient_normals: off must be host integers (a list, an array or a CPU tensor)")
-        off = off.numpy()
-    pts = _f32c(pts, "pts")
-    normals = _f32c(normals, "normals")
-    if pts.dim() != 2 or pts.shape[1] != 3:
-        raise ValueError("orient_normals expects (total,3) points, got %s" % (tuple(pts.shape),))
+    pts, normals, off, S, k = _orient_args("orient_normals", pts, off, idx, k, normals)
     total = pts.shape[0]
-    if tuple(normals.shape) != (total, 3):
-        raise ValueError("orient_normals expects (%d,3) normals, got %s" % (total, tuple(normals.shape)))
-    k = int(k)
-    if not ORIENT_MIN_K <= k <= ORIENT_MAX_K:
-        raise ValueError("orient_normals: k must be %d .. %d, got %d" % (ORIENT_MIN_K, ORIENT_MAX_K, k))
-    if idx.dtype != torch.int32:
-        raise TypeError("idx must be int32, got %s" % idx.dtype)
-    if tuple(idx.shape) != (total, k):
-        raise ValueError("orient_normals expects (%d,%d) neighbour indices, got %s" % (total, k, tuple(idx.shape)))
-    off = np.asarray(off, np.int64).reshape(-1)
-    S = off.shape[0] - 1
-    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
-        raise ValueError("orient_normals: off must ascend from 0 to %d" % total)
-    if total * max(k, 3) >= 2 ** 31:
-        raise ValueError("orient_normals: int32 offsets")
     dev = pts.device
     out = torch.empty((total, 3), dtype=torch.float32, device=dev)
     flip = torch.empty(total, dtype=torch.int32, device=dev) if want_flags else None
@@ -248,13 +257,39 @@ def orient_normals(pts, off, idx, k, normals, want_flags=False):
         lib = _lib.load()
         limit = lib.pn_orient_normals_max_points()
         if int(np.diff(off).max()) > limit:
-            raise ValueError("orient_normals: a cloud of %d points; one workgroup orients at most %d points"
-                             % (int(np.diff(off).max()), limit))
+            raise ValueError("orient_normals: a cloud of %d points; one workgroup orients at most %d points "
+                             "(the global-memory engine, orient_normals_global or engine=\"global\" / \"auto\", has no "
+                             "limit)" % (int(np.diff(off).max()), limit))
         table = _lib.h2d(off.astype(np.int32), dev)
         with _lib.on_device(dev):
             rc = lib.pn_orient_normals_f32(ptr(pts), ptr(table), S, total, ptr(idx.contiguous()), k, ptr(normals),
                                            ptr(out), ptr(flip), ptr(seed), current_stream(dev))
         check(rc, "pn_orient_normals_f32")
+    return (out, flip, seed) if want_flags else out
+
+
+def orient_normals_global(pts, off, idx, k, normals, want_flags=False):
+    """``orient_normals`` on segments of any size: the same definition and the same bits from the global-memory engine
+    (csrc/orient_global.hip, steps and schedule csrc/orient_global_math.h).  The same arguments, checks and results,
+    without the limit on the points of a segment; total * k < 2^31.  The workspace (linear in total) is allocated
+    here; ``pn_orient_normals_global_launches(largest segment)`` stream-ordered launches, no host synchronisation."""
+    import numpy as np
+    pts, normals, off, S, k = _orient_args("orient_normals_global", pts, off, idx, k, normals)
+    total = pts.shape[0]
+    dev = pts.device
+    out = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    flip = torch.empty(total, dtype=torch.int32, device=dev) if want_flags else None
+    seed = torch.empty(total, dtype=torch.int32, device=dev) if want_flags else None
+    if total > 0:
+        lib = _lib.load()
+        wsz = lib.pn_orient_normals_global_workspace_bytes(total, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        table = _lib.h2d(off.astype(np.int32), dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_orient_normals_global_f32(ptr(pts), ptr(table), S, total, int(np.diff(off).max()),
+                                                  ptr(idx.contiguous()), k, ptr(normals), ptr(out), ptr(flip),
+                                                  ptr(seed), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_orient_normals_global_f32")
     return (out, flip, seed) if want_flags else out
 
 

@@ -12,9 +12,12 @@ network trained on outward normals need oriented normals.  A viewpoint the whole
 scan from one side; for a closed shape, which no single viewpoint sees, ``orient_normals`` (or
 ``estimate_normals(..., orient="mst")``) propagates the signs along the minimum spanning forest of the k-NN graph
 under the weight 1 - |n_i . n_j| (Hoppe et al. 1992) and lets the topmost point of every connected component look up:
-one more launch (csrc/orient.hip, definition csrc/orient_math.h), outputs exactly defined.  The method's known
-weakness stays: the tree can cross a sharp crease or a thin wall with the wrong sign, and an open patch gets a
-consistent but arbitrary side."""
+one more launch (csrc/orient.hip, definition csrc/orient_math.h), outputs exactly defined.  That kernel keeps a whole
+cloud in one workgroup's LDS and stops at 10 240 points; ``engine="global"`` / ``"auto"`` runs the same definition
+from global memory over many workgroups (csrc/orient_global.hip: a fixed, stream-ordered schedule of O(log n) Boruvka
+rounds), the same bits on clouds of any size — a raw scan is
+``estimate_normals(pts, orient="mst", search="auto", engine="auto")``.  The method's known weakness stays: the tree can
+cross a sharp crease or a thin wall with the wrong sign, and an open patch gets a consistent but arbitrary side."""
 import numpy as np
 import torch
 
@@ -83,6 +86,20 @@ def _search(search, sizes, who):
     return "grid" if search == "grid" or (search == "auto" and big) else "brute"
 
 
+def _check_engine(engine, who):
+    if engine not in (None, "global", "auto"):
+        raise ValueError("%s: engine must be None, \"global\" or \"auto\", got %r" % (who, engine))
+
+
+def _engine(engine, sizes):
+    """The orientation engine of a call (``engine`` has been checked): ``K.orient_normals`` (one workgroup per cloud;
+    it raises above its limit) or ``K.orient_normals_global``."""
+    if engine == "auto":
+        big = bool(sizes) and max(sizes) > _lib.load().pn_orient_normals_max_points()
+        return K.orient_normals_global if big else K.orient_normals
+    return K.orient_normals_global if engine == "global" else K.orient_normals
+
+
 def _neighbours(flat, sizes, k, search="brute"):
     """One neighbour search over the ragged batch: (host offsets (S+1) int64, idx (total,k) int32)."""
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -102,7 +119,7 @@ def _shaped(out, layout, sizes):
     return tuple(out)
 
 
-def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None, search=None):
+def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None, search=None, engine=None):
     """Normals of a cloud that has none.
 
     points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
@@ -112,8 +129,10 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
        tensors: the normal of point p is flipped iff n . (viewpoint - p) < 0.
     orient: None, or "mst": the canonical-sign normals are oriented consistently over every cloud as ``orient_normals``
        does, on the neighbours this call has already found — one more launch.  Not together with a viewpoint, which
-       already signs every point.  Its own limit stays whatever the search: a cloud above
+       already signs every point.  Its own limit stays whatever the search: with ``engine=None`` a cloud above
        ``pn_orient_normals_max_points()`` (10 240) points is a ValueError.
+    engine: only with orient="mst" — None, "global" or "auto" as in ``orient_normals``; "global" and "auto" lift the
+       limit.  ``search`` and ``engine`` are independent.
     search: the neighbour search.  None — the brute-force kernel (csrc/knn3.hip), at most 10 240 points per cloud;
        "grid" — the uniform-grid search (csrc/knn3_grid.hip), the same neighbours bit for bit on clouds of any size;
        "auto" — brute force when every cloud has at most 10 240 points, the grid otherwise.  The result does not depend
@@ -127,22 +146,27 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
     if orient is not None and viewpoint is not None:
         raise ValueError("estimate_normals: orient=\"mst\" together with a viewpoint (a viewpoint already signs every "
                          "point)")
+    _check_engine(engine, "estimate_normals")
+    if engine is not None and orient is None:
+        raise ValueError("estimate_normals: engine=%r without orient=\"mst\" (the engine is the orientation's)"
+                         % (engine,))
     layout, sizes, flat = _clouds(points, "estimate_normals")
     k = int(k)
     if not K.NORMALS_MIN_K <= k <= K.NORMALS_MAX_K:
         raise ValueError("estimate_normals: k must be %d .. %d, got %d" % (K.NORMALS_MIN_K, K.NORMALS_MAX_K, k))
     search = _search(search, sizes, "estimate_normals")
+    orienter = _engine(engine, sizes) if orient == "mst" else None
     view = _viewpoints(viewpoint, len(sizes), flat.device)
     off, idx = _neighbours(flat, sizes, k, search)
     out = K.point_normals(flat, off, idx, k, viewpoints=view, want_scalars=return_scalars)
     out = out if return_scalars else (out,)
     if orient == "mst":
-        out = (K.orient_normals(flat, off, idx, k, out[0]),) + tuple(out[1:])
+        out = (orienter(flat, off, idx, k, out[0]),) + tuple(out[1:])
     out = _shaped(out, layout, sizes)
     return tuple(out) if return_scalars else out[0]
 
 
-def orient_normals(points, normals, k=16, return_flags=False, search=None):
+def orient_normals(points, normals, k=16, return_flags=False, search=None, engine=None):
     """Consistent orientation of normals without a viewpoint: spanning-tree propagation (Hoppe et al. 1992).
 
     points, normals: (N,3) or (B,N,3) fp32 on the GPU, or lists of (N_b,3) tensors, in the same layout; the normals may
@@ -157,7 +181,13 @@ def orient_normals(points, normals, k=16, return_flags=False, search=None):
     (N,), (B,N) or a list.  One neighbour search and one launch of csrc/orient.hip, no host synchronisation.
     search: None, "grid" or "auto" as in ``estimate_normals`` — the same neighbours, hence the same result.
     Limits: the tree can cross a sharp crease or a thin wall with the wrong sign; an open patch gets a consistent but
-    arbitrary side; a cloud above ``pn_orient_normals_max_points()`` (10 240) points is a ValueError."""
+    arbitrary side.
+    engine: None — the one-workgroup kernel (csrc/orient.hip); a cloud above ``pn_orient_normals_max_points()``
+       (10 240) points is a ValueError.  "global" — the global-memory engine (csrc/orient_global.hip) on every cloud:
+       the same definition on clouds of any size, a fixed schedule of stream-ordered launches.  "auto" — the
+       one-workgroup kernel when every cloud has at most 10 240 points, the global engine for the whole call
+       otherwise.  The result never depends on the engine."""
+    _check_engine(engine, "orient_normals")
     layout, sizes, flat = _clouds(points, "orient_normals")
     n_layout, n_sizes, n_flat = _clouds(normals, "orient_normals", "normals")
     if (n_layout, n_sizes) != (layout, sizes):
@@ -166,7 +196,8 @@ def orient_normals(points, normals, k=16, return_flags=False, search=None):
     if not K.ORIENT_MIN_K <= k <= K.ORIENT_MAX_K:
         raise ValueError("orient_normals: k must be %d .. %d, got %d" % (K.ORIENT_MIN_K, K.ORIENT_MAX_K, k))
     search = _search(search, sizes, "orient_normals")
+    orienter = _engine(engine, sizes)
     off, idx = _neighbours(flat, sizes, k, search)
-    out = K.orient_normals(flat, off, idx, k, n_flat, want_flags=return_flags)
+    out = orienter(flat, off, idx, k, n_flat, want_flags=return_flags)
     out = _shaped(out if return_flags else (out,), layout, sizes)
     return tuple(out) if return_flags else out[0]
