@@ -897,6 +897,32 @@ int pn_orient_normals_global_f32(const float* pts, const int* off, int S, int to
                                  int k, const float* normals_in, float* normals_out, int32_t* flip, int32_t* seed,
                                  void* ws, long long ws_bytes, void* stream);
 
+/* ---- farthest-point sampling of clouds of any size, with the nearest sample of every point (csrc/fps.hip,
+ * definition: csrc/fps_math.h) ----------------------------------------------------------------------------------------
+ * pts (total,3) fp32, off (S+1) DEVICE int32 row offsets from 0 to total, max_n >= the largest segment (kept for
+ * symmetry with pn_knn3_grid_f32: nothing is sized by it), m >= 1 samples per segment, start (S) int32 LOCAL indices
+ * or NULL (0); a start outside its segment is clamped into it.  Per segment of n points, m_c = min(m, n), under
+ * d(i,j) = ((x_i-x_j)^2 + (y_i-y_j)^2) + (z_i-z_j)^2, every operation rounded once in fp32, no fma: every point starts
+ * with D = +inf and owner -1; for t = 0 .. m_c-1: radius_t = D of s_t, s_t becomes chosen (D = 0, owner = t), every
+ * unchosen i with d(i, s_t) < D_i (strict) takes that D and owner t, and s_{t+1} is the unchosen point of largest D, the
+ * lowest index on equal D.  sample (S,m) int32 LOCAL indices in selection order, -1 from m_c on; radius (S,m) fp32 or
+ * NULL, +inf at t = 0, NaN where sample is -1; owner (total) int32 or NULL: the rank of the nearest sample, ties to the
+ * earliest rank; dist (total) fp32 or NULL: the final D.  A segment that holds a non-finite coordinate: sample -1,
+ * radius NaN, owner -1, dist NaN throughout.  owner and dist of a point that no valid segment of off holds are not
+ * written.  All outputs are functions of the input alone: the same bits from run to run and for every batching.
+ * pn_fps_launches(m) = m + 2 stream-ordered kernel launches (one memset comes on top), one per sample between an init
+ * and an output launch, each over all segments; it needs no GPU.  No host synchronisation, no cooperative launch, no
+ * waiting between workgroups; the candidates of a step meet in one 64-bit integer atomicMax per workgroup.  Workspace
+ * of pn_fps_workspace_bytes(total, S, m) bytes: 8 S (m + 2) of slots + 4 total + 8 (total / 1024 + S) + 16; S (m + 2)
+ * must stay below 2^59 so that the slots' byte count fits a long long (pn_fps_workspace_bytes returns 0 beyond it).
+ * PN_ERR_ARG (before any launch) for m < 1, S < 0, total < 0 (a total of 2^31 or more does not fit the int), max_n < 0,
+ * S (m + 2) >= 2^59, a NULL pts, off, sample or ws, or a workspace that is too small; S == 0 returns 0 without a
+ * launch. */
+long long pn_fps_workspace_bytes(long long total, int S, int m);
+int pn_fps_launches(int m);
+int pn_fps_f32(const float* pts, const int* off, int S, int total, int max_n, int m, const int32_t* start,
+               int32_t* sample, float* radius, int32_t* owner, float* dist, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,5 +21,5 @@ extern "C" const char* pn_last_error(void) { return g_err; }
 // 22: trimmed surfaces (pn_grid_occupancy_ragged_f32, pn_trimesh_area_f64, pn_trimesh_sample_f64)
 // 23: point coverage of the fitted primitives (pn_point_primitive_min_f32)
 //     (added symbols, no declaration changed: pn_trimesh_*, pn_point_normals_f32, pn_orient_normals_f32,
-//      pn_knn3_grid_f32, pn_knn3_grid_workspace_bytes, pn_orient_normals_global_*)
+//      pn_knn3_grid_f32, pn_knn3_grid_workspace_bytes, pn_orient_normals_global_*, pn_fps_*)
 extern "C" int pn_abi_version(void) { return PN_ABI_VERSION; }

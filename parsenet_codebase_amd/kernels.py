@@ -293,6 +293,51 @@ def orient_normals_global(pts, off, idx, k, normals, want_flags=False):
     return (out, flip, seed) if want_flags else out
 
 
+def fps_ragged(pts, off, max_n, m, start=None, want_owner=False, want_radius=False):
+    """Farthest-point sampling of every segment of a ragged batch (csrc/fps.hip, definition csrc/fps_math.h), exact and
+    bit-reproducible.  pts (total,3) fp32, off (S+1) int32 device offsets, max_n >= the largest segment (a host
+    integer), m >= 1 samples per segment, start None (0) or (S,) int32 LOCAL indices (clamped into the segment).
+    Returns sample (S,m) int32 LOCAL indices in selection order, -1 past min(m, n) — and, with ``want_owner``, owner
+    (total,) int32, the rank of every point's nearest sample, and dist (total,) fp32, the squared distance to it; with
+    ``want_radius`` radius (S,m) fp32 last, the distance of every sample to the earlier ones when it was chosen (+inf
+    first, NaN where sample is -1).  A segment that holds a non-finite coordinate: -1 and NaN throughout.
+    ``pn_fps_launches(m)`` = m + 2 stream-ordered launches on a workspace allocated here, no host synchronisation."""
+    require_cuda(pts, off, start)
+    pts = _f32c(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("fps_ragged expects (total,3) points, got %s" % (tuple(pts.shape),))
+    if off.dtype != torch.int32:
+        raise TypeError("off must be int32")
+    m = int(m)
+    if m < 1:
+        raise ValueError("fps_ragged: m = %d (m >= 1)" % m)
+    S = off.numel() - 1
+    total = pts.shape[0]
+    if total >= 2 ** 31:
+        raise ValueError("fps_ragged: total = %d (below 2^31)" % total)
+    if start is not None:
+        if start.dtype != torch.int32:
+            raise TypeError("start must be int32")
+        if tuple(start.shape) != (S,):
+            raise ValueError("fps_ragged: start must be (%d,), got %s" % (S, tuple(start.shape)))
+        start = start.contiguous()
+    dev = pts.device
+    sample = torch.empty((max(S, 0), m), dtype=torch.int32, device=dev)
+    radius = torch.empty((max(S, 0), m), dtype=torch.float32, device=dev) if want_radius else None
+    owner = torch.empty(total, dtype=torch.int32, device=dev) if want_owner else None
+    dist = torch.empty(total, dtype=torch.float32, device=dev) if want_owner else None
+    if S > 0:
+        lib = _lib.load()
+        wsz = lib.pn_fps_workspace_bytes(total, S, m)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_fps_f32(ptr(pts), ptr(off.contiguous()), S, total, int(max_n), m, ptr(start), ptr(sample),
+                                ptr(radius), ptr(owner), ptr(dist), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_fps_f32")
+    out = (sample,) + ((owner, dist) if want_owner else ()) + ((radius,) if want_radius else ())
+    return out if len(out) > 1 else sample
+
+
 def _i64c(t, name):
     if t.dtype != torch.int64:
         raise TypeError("%s must be int64, got %s" % (name, t.dtype))

@@ -1,0 +1,155 @@
+"""Reduce a scan of any size to the network's size and carry the results back: farthest-point sampling on the GPU.
+
+The segmentation network, the mean-shift stage and the fitting stage are built around some 10 000 points per shape; a
+raw scan holds a hundred times as many.  A random choice (``trainer._subsample``) reproduces the scan's uneven density
+and drops thin parts.  ``farthest_point_sample`` picks m points that cover the cloud — every next sample is the point
+farthest from the samples so far — and, while it runs, knows for every scanned point which sample is nearest: that
+"owner" is the lift of per-sample results (labels, primitive ids, membership rows) back to full resolution.
+
+    reduced, normals_r, owner = reduce_cloud(scan, 10000, normals)      # before the network
+    labels_full = lift(labels_of_reduced, owner)                        # after it
+
+The definition (csrc/fps_math.h) is exact and bit-reproducible: squared distances
+((x_i-x_j)^2 + (y_i-y_j)^2) + (z_i-z_j)^2 rounded once per operation in fp32, strict updates, the lowest index on equal
+distances.  csrc/fps.hip runs it from global memory over many workgroups, so no cloud size is a limit.
+
+Limits.  The sampling is sequential in m: m + 2 stream-ordered launches.  It picks outliers first: a scan with stray
+points should go through an outlier statistic before it.  ``owner`` is the nearest SAMPLE, not a surface projection:
+lifting labels across a thin wall follows Euclidean distance."""
+import numbers
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import kernels as K
+from .point_normals import _clouds, _shaped
+
+
+def _flat_clouds(points, who):
+    """_clouds with this module's errors: a non-fp32 dtype is a TypeError."""
+    for c in (points if isinstance(points, (list, tuple)) else [points]):
+        if torch.is_tensor(c) and c.is_cuda and c.dtype != torch.float32:
+            raise TypeError("%s: points must be float32, got %s" % (who, c.dtype))
+    return _clouds(points, who)
+
+
+def _starts(start, S, device, who):
+    """None, an int or one int per cloud -> None or (S,) int32 on the device."""
+    if start is None:
+        return None
+    if isinstance(start, numbers.Integral) and not isinstance(start, bool):
+        start = [int(start)] * S
+    elif isinstance(start, (list, tuple, np.ndarray)) or torch.is_tensor(start):
+        start = start.tolist() if isinstance(start, np.ndarray) or torch.is_tensor(start) else list(start)
+        if not isinstance(start, list) or len(start) != S:
+            raise ValueError("%s: start holds one index per cloud (%d)" % (who, S))
+        if not all(isinstance(s, numbers.Integral) and not isinstance(s, bool) for s in start):
+            raise ValueError("%s: start must be None, an int or one int per cloud, got %r" % (who, start))
+    else:
+        raise ValueError("%s: start must be None, an int or one int per cloud, got %r" % (who, start))
+    return _lib.h2d(np.clip(np.asarray(start, dtype=np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32), device)
+
+
+def _samples(points, m, start, who, want_owner, want_radius, full=False):
+    if isinstance(m, bool) or not isinstance(m, numbers.Integral) or m < 1:
+        raise ValueError("%s: m must be an integer >= 1, got %r" % (who, m))
+    layout, sizes, flat = _flat_clouds(points, who)
+    if full and min(sizes) < m:
+        raise ValueError("%s: a cloud of %d points cannot give m = %d samples" % (who, min(sizes), m))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    start = _starts(start, len(sizes), flat.device, who)
+    out = K.fps_ragged(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), int(m), start=start,
+                       want_owner=want_owner, want_radius=want_radius)
+    return layout, sizes, flat, off, (out if isinstance(out, tuple) else (out,))
+
+
+def _per_cloud(rows, layout):
+    """(S,m,...) results back in the layout of the input."""
+    if isinstance(layout, tuple):
+        return rows
+    return list(rows.unbind(0)) if layout == "list" else rows[0]
+
+
+def farthest_point_sample(points, m, start=None, return_owner=False, return_radius=False):
+    """Farthest-point sampling of every cloud.
+
+    points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
+    m: samples per cloud, >= 1.  A cloud of n < m points gives its n points and -1 in the other entries.
+    start: the first sample — None (point 0), an int, or one int per cloud; clamped into the cloud.
+    Returns ``sample``, int64 indices into the cloud in selection order: (m,), (B,m) or a list of (m,), so that
+    ``points[sample]`` works on a single cloud.  With ``return_owner`` also ``owner`` (int64, per point: the rank in
+    ``sample`` of the nearest sample, ties to the earliest) and ``dist`` (fp32, the squared distance to it), in the
+    layout of the points: (N,), (B,N) or a list.  With ``return_radius`` also ``radius`` last, in the layout of
+    ``sample``: the squared distance of every sample to the earlier ones when it was chosen (+inf first, then
+    non-increasing; the last one bounds every ``dist``), NaN where ``sample`` is -1.
+    A cloud that holds a non-finite coordinate gets -1 and NaN throughout.  All results are functions of the input
+    alone.  m + 2 stream-ordered launches, no host synchronisation."""
+    who = "farthest_point_sample"
+    layout, sizes, _, _, out = _samples(points, m, start, who, return_owner, return_radius)
+    res = [_per_cloud(out[0].long(), layout)]
+    if return_owner:
+        res += list(_shaped((out[1].long(), out[2]), layout, sizes))
+    if return_radius:
+        res.append(_per_cloud(out[-1], layout))
+    return tuple(res) if len(res) > 1 else res[0]
+
+
+def reduce_cloud(points, m, *per_point, start=None):
+    """The one call in front of the network: (points[sample], *[a[sample] for a in per_point], owner).
+
+    points, m, start: as in ``farthest_point_sample``.  per_point: arrays with one row per point (normals, colours,
+    labels) in the layout of ``points``: (N,...), (B,N,...) or lists of (N_b,...).  The reduced arrays come back as
+    (m,...), (B,m,...) or lists of (m,...); ``owner`` as in ``farthest_point_sample`` — keep it for ``lift``.
+    Raises ValueError if a cloud has fewer than m points (a -1 index would gather the wrong row silently)."""
+    who = "reduce_cloud"
+    layout, sizes, flat, off, out = _samples(points, m, start, who, True, False, full=True)
+    S = len(sizes)
+    rows = (out[0].long() + _lib.h2d(off[:-1], flat.device)[:, None]).reshape(-1)      # rows of the flat arrays
+    res = []
+    for a in (points,) + per_point:
+        if isinstance(a, (list, tuple)):
+            if layout != "list" or [int(x.shape[0]) for x in a] != sizes:
+                raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
+            a = a[0] if len(a) == 1 else torch.cat(list(a))
+        elif not torch.is_tensor(a):
+            raise TypeError("%s: a per-point array must be a tensor or a list of tensors" % who)
+        elif isinstance(layout, tuple):
+            if tuple(a.shape[:2]) != layout:
+                raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
+            a = a.reshape((-1,) + tuple(a.shape[2:]))
+        elif layout != "single" or a.shape[0] != sizes[0]:
+            raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
+        _lib.require_cuda(a)
+        res.append(_per_cloud(a[rows].reshape((S, int(m)) + tuple(a.shape[1:])), layout))
+    return tuple(res) + (_shaped((out[1].long(),), layout, sizes)[0],)
+
+
+def lift(values, owner):
+    """Per-sample values to per-point values: ``values[owner]`` per cloud, over any trailing shape.
+
+    values: (m,...), (B,m,...) or a list of (m_b,...) tensors — labels, primitive ids, membership rows of the reduced
+    cloud; owner: what ``farthest_point_sample`` / ``reduce_cloud`` returned, (N,), (B,N) or a list of (N_b,).
+    Returns (N,...), (B,N,...) or a list.  Raises ValueError where owner holds -1 (a cloud with a non-finite
+    coordinate) or a rank past the values."""
+    if isinstance(owner, (list, tuple)):
+        if not isinstance(values, (list, tuple)) or len(values) != len(owner):
+            raise ValueError("lift: a list of owners takes a list of as many value tensors")
+        return [lift(v, o) for v, o in zip(values, owner)]
+    if not torch.is_tensor(owner) or not torch.is_tensor(values):
+        raise TypeError("lift: values and owner must be tensors or lists of tensors")
+    if owner.dtype not in (torch.int64, torch.int32):
+        raise TypeError("lift: owner must be an integer tensor, got %s" % owner.dtype)
+    if owner.dim() not in (1, 2) or values.dim() < owner.dim() or (owner.dim() == 2
+                                                                    and values.shape[0] != owner.shape[0]):
+        raise ValueError("lift: owner (N,) with values (m,...), or owner (B,N) with values (B,m,...); got %s and %s"
+                         % (tuple(owner.shape), tuple(values.shape)))
+    m = values.shape[owner.dim() - 1]
+    if owner.numel() and (int(owner.min()) < 0 or int(owner.max()) >= m):
+        raise ValueError("lift: owner holds -1 or a rank past the %d values (a cloud without samples?)" % m)
+    owner = owner.long()
+    if owner.dim() == 1:
+        return values[owner]
+    B, N = owner.shape
+    rows = (owner + torch.arange(B, device=owner.device)[:, None] * m).reshape(-1)
+    return values.reshape((B * m,) + tuple(values.shape[2:]))[rows].reshape((B, N) + tuple(values.shape[2:]))

@@ -1,0 +1,288 @@
+"""CPU-side checks of the farthest-point sampling: csrc/fps_math.h compiled for the host into a serial restatement of
+the kernels' schedule (tests/native/fps_host.cpp: tile table, per-tile candidates, the maximum over 64-bit keys, the
+decoding of the slots) against ``fps_numpy``, an independent numpy restatement of the definition (a plain loop with an
+argmax that takes the first maximum) — every output exactly equal, in both tile orders —, the three exact properties
+of the definition, the stand-alone program, the export of csrc/fps.hip and its argument checks."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.test_knn3_grid_abi import collinear, copies_among_random, lattice, offset_cloud, planar
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCE = os.path.join(ROOT, "tests", "native", "fps_host.cpp")
+NAMES = ("pn_fps_f32", "pn_fps_workspace_bytes", "pn_fps_launches")
+TILE = 1024      # FPS_TILE of csrc/fps_math.h (test_the_tile_is_the_one_the_tests_assume)
+
+
+# ---------------------------------------------------------------------------------------------
+# the definition, in numpy (shared with tests/test_fps_gpu.py)
+# ---------------------------------------------------------------------------------------------
+def fps_numpy(P, m, start=0):
+    """One cloud by the definition: (sample (m) int32, radius (m) fp32, owner (n) int32, dist (n) fp32).
+    d = ((dx*dx + dy*dy) + dz*dz) on float32 arrays, every operation rounded once; strict updates; the next sample is
+    np.argmax over the unchosen points, which takes the first maximum."""
+    P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+    n = P.shape[0]
+    sample, radius = np.full(m, -1, np.int32), np.full(m, np.nan, np.float32)
+    owner = np.full(n, -1, np.int32)
+    if not np.isfinite(P).all():
+        return sample, radius, owner, np.full(n, np.nan, np.float32)
+    D = np.full(n, np.inf, np.float32)
+    if n == 0:
+        return sample, radius, owner, D
+    chosen = np.zeros(n, bool)
+    s = min(max(int(start), 0), n - 1)
+    x, y, z = P[:, 0], P[:, 1], P[:, 2]
+    with np.errstate(over="ignore"):
+        for t in range(min(m, n)):
+            sample[t], radius[t] = s, D[s]
+            chosen[s], D[s], owner[s] = True, 0.0, t
+            dx, dy, dz = x - x[s], y - y[s], z - z[s]
+            nd = (dx * dx + dy * dy) + dz * dz
+            assert nd.dtype == np.float32
+            take = ~chosen & (nd < D)
+            D[take], owner[take] = nd[take], t
+            s = int(np.argmax(np.where(chosen, np.float32(-1), D)))
+    return sample, radius, owner, D
+
+
+def fps_numpy_batch(clouds, m, start=None):
+    """A ragged batch: (sample (S,m), radius (S,m), owner (total), dist (total))."""
+    start = [0] * len(clouds) if start is None else start
+    out = [fps_numpy(c, m, s) for c, s in zip(clouds, start)]
+    return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]),
+            np.concatenate([o[2] for o in out]), np.concatenate([o[3] for o in out]))
+
+
+def same(a, b):
+    """Exact equality of two arrays; NaN equals NaN for the floating-point ones."""
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+def check_properties(P, sample, radius, dist):
+    """The three exact properties on one finite cloud with at least one sample."""
+    mc = int((sample >= 0).sum())
+    assert mc >= 1 and (sample[:mc] >= 0).all() and (sample[mc:] == -1).all() and np.isnan(radius[mc:]).all()
+    assert len(set(sample[:mc].tolist())) == mc                                  # never chosen twice
+    assert np.isposinf(radius[0]) and (np.diff(radius[1:mc]) <= 0).all()          # (1)
+    Q = P[sample[:mc]].astype(np.float32)
+    dx, dy, dz = (Q[:, None, a] - Q[None, :, a] for a in range(3))
+    d = (dx * dx + dy * dy) + dz * dz
+    t, u = np.triu_indices(mc, 1)
+    assert (d[t, u] >= radius[u]).all()                                          # (2)
+    assert (dist <= radius[mc - 1]).all() and (dist[sample[:mc]] == 0).all()     # (3)
+
+
+def clouds():
+    """name -> cloud: the adversarial inputs and sizes on both sides of the tile."""
+    rng = np.random.RandomState(21)
+    out = {
+        "lattice": lattice(11),                                  # 1 331 points: two tiles, all ties
+        "copies among random": copies_among_random(600, 400),
+        "offset, 1e-4 spacing": offset_cloud(700),
+        "planar": planar(500),
+        "collinear": collinear(300),
+        "huge coordinates": (rng.uniform(-1, 1, (50, 3)) * 3e38).astype(np.float32),      # d overflows to +inf
+    }
+    for n in (1, 2, 3, 65, TILE - 1, TILE, TILE + 1, 2 * TILE + 1):
+        out["uniform %d" % n] = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the host-compiled header
+# ---------------------------------------------------------------------------------------------
+def build_harness(directory):
+    out = os.path.join(str(directory), "libfph.so")
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
+    return ctypes.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return build_harness(tmp_path_factory.mktemp("fph"))
+
+
+def host_fps(lib, batch, m, start=None, order=0):
+    sizes = [c.shape[0] for c in batch]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    S, total = len(batch), int(off[-1])
+    P = np.ascontiguousarray(np.concatenate([c.reshape(-1, 3) for c in batch]), np.float32)
+    st = None if start is None else np.asarray(start, np.int32)
+    sample, radius = np.empty((S, m), np.int32), np.empty((S, m), np.float32)
+    owner, dist = np.empty(total, np.int32), np.empty(total, np.float32)
+    p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+    rc = lib.fph_fps(p(P), p(off), S, total, m, p(st), order, p(sample), p(radius), p(owner), p(dist))
+    assert rc == m + 2 == lib.fph_launches(m)
+    return sample, radius, owner, dist
+
+
+def test_the_tile_is_the_one_the_tests_assume(harness):
+    assert harness.fph_tile() == TILE
+
+
+@pytest.mark.parametrize("name", sorted(clouds()))
+def test_the_restated_schedule_equals_the_definition(harness, name):
+    P = clouds()[name]
+    n = P.shape[0]
+    for m in sorted({1, 2, 17, max(n - 1, 1), n, n + 5} if n <= 65 else {1, 17, 40}):
+        want = fps_numpy_batch([P], m)
+        for order in (0, 1):
+            got = host_fps(harness, [P], m, order=order)
+            assert all(same(g, w) for g, w in zip(got, want)), (name, m, order)
+        if name != "huge coordinates":
+            check_properties(P, want[0][0], want[1][0], want[3])
+
+
+def tied_candidates(P, sample):
+    """The unchosen points that tie for the largest D after the samples given: indices ascending."""
+    P = P.astype(np.float32)
+    dx, dy, dz = (P[:, None, a] - P[None, sample, a] for a in range(3))
+    D = ((dx * dx + dy * dy) + dz * dz).min(1)
+    D[sample] = -1
+    return np.flatnonzero(D == D.max())
+
+
+def test_ties_on_the_lattice_go_to_the_lowest_index_across_tiles(harness):
+    P = lattice(11)
+    for order in (0, 1):
+        sample = host_fps(harness, [P], 3, order=order)[0][0]
+        tied = tied_candidates(P, sample[:2])
+        assert len(tied) > 1 and tied[0] < TILE <= tied[-1]            # the tie spans two tiles (workgroups)
+        assert sample[2] == tied[0]
+    assert same(sample, fps_numpy(P, 3)[0])
+
+
+def test_a_ragged_batch_with_empty_short_and_non_finite_clouds(harness):
+    rng = np.random.RandomState(5)
+    nan, inf = rng.uniform(-1, 1, (40, 3)).astype(np.float32), rng.uniform(-1, 1, (TILE + 7, 3)).astype(np.float32)
+    nan[11, 1], inf[TILE + 2, 0] = np.nan, -np.inf
+    batch = [rng.uniform(-1, 1, (TILE + 300, 3)).astype(np.float32), np.zeros((0, 3), np.float32), nan,
+             rng.uniform(-1, 1, (5, 3)).astype(np.float32), inf, lattice(5)]
+    start = [7, 0, 3, 99, 1, -4]                                                  # in range, clamped above and below
+    want = fps_numpy_batch(batch, 9, start)
+    for order in (0, 1):
+        got = host_fps(harness, batch, 9, start, order)
+        assert all(same(g, w) for g, w in zip(got, want))
+    assert (want[0][[1, 2, 4]] == -1).all() and (want[0][3][5:] == -1).all() and (want[0][3][:5] >= 0).all()
+    assert want[0][0][0] == 7 and want[0][3][0] == 4 and want[0][5][0] == 0      # start: kept, clamped, clamped
+    # every cloud alone gives what it gives in the batch
+    o = 0
+    for c, (P, s) in enumerate(zip(batch, start)):
+        alone = host_fps(harness, [P], 9, [s])
+        n = P.shape[0]
+        assert same(alone[0][0], want[0][c]) and same(alone[1][0], want[1][c])
+        assert same(alone[2], want[2][o:o + n]) and same(alone[3], want[3][o:o + n])
+        o += n
+
+
+def test_the_program_checks_itself_and_reads_a_file(harness, tmp_path):
+    exe = str(tmp_path / "fps_host")
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "0 differences" in run.stdout, run.stdout
+    P, m = offset_cloud(150), 12
+    path = tmp_path / "cloud.txt"
+    path.write_text("%d %d %d\n" % (P.shape[0], m, 4) + "".join("%.9g %.9g %.9g\n" % tuple(p) for p in P))
+    run = subprocess.run([exe, str(path)], capture_output=True, text=True, check=True)
+    assert [int(x) for x in run.stdout.split()] == fps_numpy(P, m, 4)[0].tolist()
+
+
+# ---------------------------------------------------------------------------------------------
+# the export and the argument checks, which run before anything touches a GPU
+# ---------------------------------------------------------------------------------------------
+def load_raw():
+    """The library through a private ctypes handle, the entry points bound from the header's table."""
+    from parsenet_codebase_amd import _lib
+    _lib.load()
+    handle = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NAMES + ("pn_abi_version",):
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    handle.pn_last_error.restype = ctypes.c_char_p
+    return handle
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_raw()
+
+
+def test_the_entry_points_are_exported_and_bound(lib):
+    from parsenet_codebase_amd import _lib
+    v, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    assert _lib.SIGNATURES["pn_fps_f32"] == (i, [v, v, i, i, i, i, v, v, v, v, v, v, ll, v])
+    assert _lib.SIGNATURES["pn_fps_workspace_bytes"] == (ll, [ll, i, i])
+    assert _lib.SIGNATURES["pn_fps_launches"] == (i, [i])
+    assert lib.pn_abi_version() == 23 == _lib.CONSTANTS["PN_ABI_VERSION"]                   # added symbols only
+    assert all(hasattr(_lib.load(), n) for n in NAMES)
+    assert [lib.pn_fps_launches(m) for m in (1, 2, 512, 10000)] == [3, 4, 514, 10002]
+    w = lib.pn_fps_workspace_bytes
+    # one 64-bit slot per (cloud, step) and 4 bytes of D per point, known from (total, S, m) alone
+    assert w(1000, 3, 10) >= 8 * 3 * 10 + 4 * 1000
+    assert w(2000, 3, 10) - w(1000, 3, 10) == w(3000, 3, 10) - w(2000, 3, 10) <= 8 * 1000
+    assert w(1000, 3, 20) - w(1000, 3, 10) == 8 * 3 * 10
+    assert w(2 * 10 ** 9, 1, 1) > 2 ** 32                                                     # long long, not int
+    assert w(10, 2 ** 31 - 1, 2 ** 31 - 3) == 0 and w(10, 1, 0) == 0                        # S (m + 2) >= 2^59; m < 1
+
+
+ARGS = ("pts", "off", "S", "total", "max_n", "m", "start", "sample", "radius", "owner", "dist", "ws", "ws_bytes",
+        "stream")
+
+
+def raw_call(lib, **over):
+    """pn_fps_f32 with plausible arguments (never dereferenced by a call that is refused), some replaced."""
+    a = dict(pts=64, off=64, S=1, total=10, max_n=10, m=4, start=None, sample=64, radius=None, owner=None, dist=None,
+             ws=64, ws_bytes=lib.pn_fps_workspace_bytes(10, 1, 4), stream=None)
+    a.update(over)
+    return lib.pn_fps_f32(*[a[n] for n in ARGS])
+
+
+def check_invalid_arguments(lib, **real):
+    """m < 1, a total that does not fit, S < 0, a null required pointer, a short workspace: PN_ERR_ARG, the message
+    naming the argument; nothing to do: 0."""
+    from parsenet_codebase_amd import _lib
+    err = _lib.CONSTANTS["PN_ERR_ARG"]
+    need = lib.pn_fps_workspace_bytes(real.get("total", 10), real.get("S", 1), real.get("m", 4))
+    for over, word in ((dict(m=0), b"m=0"), (dict(m=-3), b"m=-3"), (dict(total=-1), b"total=-1"),
+                       (dict(total=-2 ** 31), b"total="), (dict(S=-1), b"S=-1"), (dict(max_n=-1), b"max_n=-1"),
+                       (dict(pts=None), b"null"), (dict(off=None), b"null"), (dict(sample=None), b"null"),
+                       (dict(ws=None), b"null"), (dict(ws_bytes=need - 1), b"workspace"),
+                       (dict(ws_bytes=0), b"workspace")):
+        assert raw_call(lib, **dict(real, **over)) == err, over
+        assert b"pn_fps_f32" in lib.pn_last_error() and word in lib.pn_last_error(), (over, lib.pn_last_error())
+    assert raw_call(lib, **dict(real, S=0)) == 0
+    assert raw_call(lib, **dict(real, S=0, pts=None, sample=None, ws=None, ws_bytes=0)) == 0
+
+
+def test_invalid_arguments_are_refused_before_any_launch(lib):
+    """(No GPU is needed to get here: a refused call, and one with nothing to do, launch nothing.)"""
+    check_invalid_arguments(lib)
+
+
+def test_python_argument_checks_need_no_gpu():
+    import torch
+    from parsenet_codebase_amd import kernels, sampling
+    with pytest.raises(RuntimeError, match="MI355X only"):
+        kernels.fps_ragged(torch.zeros(8, 3), torch.zeros(2, dtype=torch.int32), 8, 3)
+    with pytest.raises(RuntimeError, match="MI355X only"):
+        sampling.farthest_point_sample(torch.zeros(8, 3), 3)
+    with pytest.raises(RuntimeError, match="MI355X only"):
+        sampling.reduce_cloud(torch.zeros(8, 3), 3)
+    for m in (0, -1, 2.5, True):
+        with pytest.raises(ValueError, match="m must be"):
+            sampling.farthest_point_sample(torch.zeros(8, 3), m)
+    with pytest.raises(ValueError, match="owner holds -1"):
+        sampling.lift(torch.arange(4), torch.tensor([0, 3, -1]))
+    with pytest.raises(ValueError, match="owner holds -1"):
+        sampling.lift(torch.arange(4), torch.tensor([0, 4]))
+    assert sampling.lift(torch.arange(4) * 10, torch.tensor([[0, 3], [1, 1]])[0]).tolist() == [0, 30]
+    vals = torch.arange(12.0).reshape(2, 3, 2)
+    own = torch.tensor([[0, 2, 2, 1], [1, 0, 0, 2]])
+    assert torch.equal(sampling.lift(vals, own), torch.stack([vals[0][own[0]], vals[1][own[1]]]))
+    assert all(torch.equal(a, b) for a, b in zip(sampling.lift(list(vals), list(own)), [vals[0][own[0]], vals[1][own[1]]]))
