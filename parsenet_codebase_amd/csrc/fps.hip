@@ -34,27 +34,19 @@ struct FpsWs {
   int* tile_first;
 };
 
-static long long fps_ws_bytes(long long total, int S, int m) {
-  return 8 * fps_slots(m) * S + 4 * total + 8 * fps_tiles(total, S);
-}
-
-static FpsWs fps_ws(void* base, long long total, int S, int m) {
-  FpsWs w;
-  w.slot = (unsigned long long*)base;
-  w.D = (float*)(w.slot + fps_slots(m) * S);
-  w.tile_seg = (int*)(w.D + total);
-  w.tile_first = w.tile_seg + fps_tiles(total, S);
-  return w;
+// The arrays of the workspace in order, cut from `base` (0: measure only); returns their bytes.
+static long long fps_carve(void* base, long long total, int S, int m, FpsWs* w) {
+  RgCarver c = {(uintptr_t)base, 0};
+  w->slot = c.take<unsigned long long>(fps_slots(m) * S);
+  w->D = c.take<float>(total);
+  w->tile_seg = c.take<int>(fps_tiles(total, S));
+  w->tile_first = c.take<int>(fps_tiles(total, S));
+  return c.bytes;
 }
 
 // The cloud whose tile numbers hold tile b: the last c with fps_tile_base(off[c], c) <= b.
 __device__ static inline int fps_find_segment(const int* __restrict__ off, int S, long long b) {
-  int lo = 0, hi = S;
-  for (int t = 0; t < 32 && hi - lo > 1; ++t) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (fps_tile_base(off[mid], mid) <= b) lo = mid; else hi = mid;
-  }
-  return lo;
+  return rg_segment(S, b, [off](int c) { return fps_tile_base(off[c], c); });
 }
 
 __device__ static inline unsigned long long fps_block_max(unsigned long long v, unsigned long long* sh) {
@@ -164,7 +156,8 @@ __global__ __launch_bounds__(FPS_LANES) void pn_fps_output_kernel(const int* __r
 
 extern "C" long long pn_fps_workspace_bytes(long long total, int S, int m) {
   if (total < 0 || S < 0 || m < 1 || fps_slots(m) * S >= (1ll << 59)) return 0;
-  return fps_ws_bytes(total, S, m) + 16;
+  FpsWs w;
+  return fps_carve(nullptr, total, S, m, &w) + 16;
 }
 
 extern "C" int pn_fps_launches(int m) { return fps_launches(m < 0 ? 0 : m); }
@@ -183,9 +176,10 @@ extern "C" int pn_fps_f32(const float* pts, const int* off, int S, int total, in
                who);
   PN_CHECK_ARG(ws_bytes >= pn_fps_workspace_bytes(total, S, m), "%s: workspace of %lld bytes (%lld)", who, ws_bytes,
                pn_fps_workspace_bytes(total, S, m));
-  const FpsWs w = fps_ws((void*)pn_align_up((size_t)ws, 16), total, S, m);
+  FpsWs w;
+  fps_carve((void*)pn_align_up((size_t)ws, 16), total, S, m, &w);
   const dim3 block(FPS_LANES), grid((unsigned)fps_tiles(total, S));
-  PN_CHECK_HIP(hipMemsetAsync(w.slot, 0, (size_t)(8 * fps_slots(m) * S), stream));
+  PN_CHECK_HIP(hipMemsetAsync(w.slot, 0, (size_t)((char*)w.D - (char*)w.slot), stream));
   PN_PROF("fps", stream);
   hipLaunchKernelGGL(pn_fps_init_kernel, grid, block, 0, stream, pts, off, S, total, m, start, w, owner);
   for (int t = 0; t < m; ++t)

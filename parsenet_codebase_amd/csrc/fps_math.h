@@ -42,6 +42,7 @@
 // writes the flat table tile -> (segment, first point) that the m step launches read.
 #pragma once
 #include "knn3_grid_math.h"
+#include "ragged.h"
 
 #define FPS_LANES 256                          // lanes per workgroup
 #define FPS_PER_LANE 4                         // points per lane: four independent 12-byte rows in flight
@@ -68,7 +69,7 @@ KG_HD float fps_key_dist(unsigned long long key) { return kg_float((uint32_t)(ke
 KG_HD int fps_clamp_start(int s, int n) { return s < 0 ? 0 : (s > n - 1 ? n - 1 : s); }
 
 // Is (o0, o1) a segment inside 0 .. total?
-KG_HD int fps_valid_segment(int o0, int o1, int total) { return o0 >= 0 && o0 <= o1 && o1 <= total; }
+KG_HD int fps_valid_segment(int o0, int o1, int total) { return rg_valid_segment(o0, o1, total); }
 
 // Step t at point i (coordinates p, working distance *D) against the sample s (coordinates q): the new working
 // distance in *D, 1 if the point's owner becomes t, and the point's candidate key as the return value.

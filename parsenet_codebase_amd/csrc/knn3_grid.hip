@@ -30,6 +30,7 @@
 
 #include "knn3_grid_math.h"
 #include "knn_common.h"
+#include "ragged.h"
 
 #define KG_ROWS_PER_WAVE 512      // bbox: rows one wave reduces before its six atomics
 
@@ -43,40 +44,22 @@ struct KgWs {
   uint32_t* bmin;      // (S,3) ord of the minima: memset 0xff
 };
 
-static long long kg_ws_bytes(long long total, long long S) {
-  return 16 * total + 4 * total + 4 * total + 12 * S + 4 * S + 4 * (total + 2 * S) + 12 * S;
-}
-
-static KgWs kg_ws(void* ws, long long total, long long S) {
-  KgWs w;
-  char* p = (char*)ws;
-  w.rec = (float4*)p;
-  p += 16 * total;
-  w.pcell = (int*)p;
-  p += 4 * total;
-  w.prank = (int*)p;
-  p += 4 * total;
-  w.bmax = (uint32_t*)p;
-  p += 12 * S;
-  w.flag = (uint32_t*)p;
-  p += 4 * S;
-  w.start = (int*)p;
-  p += 4 * (total + 2 * S);
-  w.bmin = (uint32_t*)p;
-  return w;
+// The arrays of the workspace in order, cut from `base` (0: measure only); returns their bytes.
+static long long kg_carve(void* base, long long total, long long S, KgWs* w) {
+  RgCarver c = {(uintptr_t)base, 0};
+  w->rec = c.take<float4>(total);
+  w->pcell = c.take<int>(total);
+  w->prank = c.take<int>(total);
+  w->bmax = c.take<uint32_t>(3 * S);
+  w->flag = c.take<uint32_t>(S);
+  w->start = c.take<int>(total + 2 * S);
+  w->bmin = c.take<uint32_t>(3 * S);
+  return c.bytes;
 }
 
 // The segment of a row: the largest s < S with off[s] <= row.  The caller checks off[s] <= row < off[s + 1].
 __device__ static inline int kg_segment(const int* __restrict__ off, int S, int row) {
-  int a = 0, b = S;
-  while (b - a > 1) {
-    const int m = (a + b) >> 1;
-    if (off[m] <= row)
-      a = m;
-    else
-      b = m;
-  }
-  return a;
+  return rg_row_segment(off, S, row);
 }
 
 __device__ static inline KgGrid kg_segment_grid(const KgWs& w, int s, int n, int ppc) {
@@ -353,7 +336,8 @@ __global__ __launch_bounds__(256) void pn_knn3_grid_search_kernel(const int* __r
 // ---- host -------------------------------------------------------------------------------------------------------------------
 extern "C" long long pn_knn3_grid_workspace_bytes(long long total, int S) {
   if (total < 0 || S < 0) return 0;
-  return kg_ws_bytes(total, S) + 16;
+  KgWs w;
+  return kg_carve(nullptr, total, S, &w) + 16;
 }
 
 // PN_KNN3_GRID_PPC: developer hook of tools/knn3_grid_ab.py — the points per cell, which moves the speed and no output.
@@ -374,9 +358,10 @@ extern "C" int pn_knn3_grid_f32(const float* pts, const int* off, int S, int tot
   PN_CHECK_ARG(pts && off && idx && ws, "pn_knn3_grid_f32: null pointer");
   PN_CHECK_ARG(ws_bytes >= pn_knn3_grid_workspace_bytes(total, S), "pn_knn3_grid_f32: workspace of %lld bytes (%lld)",
                ws_bytes, pn_knn3_grid_workspace_bytes(total, S));
-  const KgWs w = kg_ws((void*)pn_align_up((size_t)ws, 16), total, S);
+  KgWs w;
+  kg_carve((void*)pn_align_up((size_t)ws, 16), total, S, &w);
   const int ppc = kg_ppc();
-  const size_t zero_bytes = (size_t)12 * S + (size_t)4 * S + (size_t)4 * ((size_t)total + 2 * (size_t)S);
+  const size_t zero_bytes = (size_t)((char*)w.bmin - (char*)w.bmax);      // box max, flag and cell starts
   PN_CHECK_HIP(hipMemsetAsync(w.bmax, 0, zero_bytes, stream));
   PN_CHECK_HIP(hipMemsetAsync(w.bmin, 0xff, (size_t)12 * S, stream));
   const int row_blocks = pn_cdiv(total, 256);

@@ -35,6 +35,7 @@
 // lower keys reach the atomic unit.
 #include "common.h"
 #include "orient_global_math.h"
+#include "ragged.h"
 
 struct OgWs {
   uint32_t* ctrl;
@@ -44,27 +45,21 @@ struct OgWs {
   int* seg;
 };
 
-static long long og_ws_bytes(long long total) { return (long long)OG_CTRL_WORDS * 4 + 20 * total; }
-
-static OgWs og_ws(void* base, long long total) {
-  OgWs w;
-  w.ctrl = (uint32_t*)base;
-  w.best = (unsigned long long*)(w.ctrl + OG_CTRL_WORDS);
-  w.P = (uint32_t*)(w.best + total);
-  w.H = w.P + total;
-  w.seg = (int*)(w.H + total);
-  return w;
+// The arrays of the workspace in order, cut from `base` (0: measure only); returns their bytes.
+static long long og_carve(void* base, long long total, OgWs* w) {
+  RgCarver c = {(uintptr_t)base, 0};
+  w->ctrl = c.take<uint32_t>(OG_CTRL_WORDS);
+  w->best = c.take<unsigned long long>(total);
+  w->P = c.take<uint32_t>(total);
+  w->H = c.take<uint32_t>(total);
+  w->seg = c.take<int>(total);
+  return c.bytes;
 }
 
 // The segment of point g: the last s with off[s] <= g, accepted only if g lies inside a segment inside 0 .. total.
 __device__ static inline int og_find_segment(const int* __restrict__ off, int S, int total, int g) {
-  int lo = 0, hi = S;                                   // off[lo] <= g (assumed for lo = 0), off[hi] > g or hi = S
-  for (int t = 0; t < 32 && hi - lo > 1; ++t) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= g) lo = mid; else hi = mid;
-  }
-  const int o0 = off[lo], o1 = off[lo + 1];
-  return (o0 >= 0 && o0 <= g && g < o1 && o1 <= total) ? lo : -1;
+  const int s = rg_row_segment(off, S, g);
+  return rg_segment_holds(off[s], off[s + 1], total, g) ? s : -1;
 }
 
 __global__ __launch_bounds__(OG_BLOCK) void pn_orient_global_init_kernel(const int* __restrict__ off, int S, int total,
@@ -182,7 +177,8 @@ __global__ __launch_bounds__(OG_BLOCK) void pn_orient_global_output_kernel(
 
 extern "C" long long pn_orient_normals_global_workspace_bytes(long long total, int S) {
   if (total < 0 || S < 0) return 0;
-  return og_ws_bytes(total) + 16;
+  OgWs w;
+  return og_carve(nullptr, total, &w) + 16;
 }
 
 extern "C" int pn_orient_normals_global_launches(int max_n) { return og_launches(max_n < 0 ? 0 : max_n); }
@@ -200,7 +196,8 @@ extern "C" int pn_orient_normals_global_f32(const float* pts, const int* off, in
   PN_CHECK_ARG(normals_in != normals_out, "%s: normals_out must not be normals_in", who);
   PN_CHECK_ARG(ws_bytes >= pn_orient_normals_global_workspace_bytes(total, S), "%s: workspace of %lld bytes (%lld)", who,
                ws_bytes, pn_orient_normals_global_workspace_bytes(total, S));
-  const OgWs w = og_ws((void*)pn_align_up((size_t)ws, 16), total);
+  OgWs w;
+  og_carve((void*)pn_align_up((size_t)ws, 16), total, &w);
   const int rounds = og_rounds(max_n), passes = og_passes(max_n);
   const dim3 block(OG_BLOCK);
   const int vb = pn_cdiv(total, OG_BLOCK), eb = pn_cdiv((long long)total * k, OG_BLOCK);

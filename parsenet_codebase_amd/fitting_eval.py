@@ -41,6 +41,7 @@ from . import mean_shift as MSM
 from ._lib import h2d
 from .fitting_batch import (CMAX, EPS, PRIM_CODE, _BSplineEval, _fitter_bases, bandwidth_batch, nms_batch,
                             standardize_segments)
+from .kernels import KNN3_MAX_POINTS
 
 _CLOSED_TYPES, _OPEN_TYPES = (0, 9, 6, 7), (2, 8)
 _RESAMPLE = {"closed": (1400, 1800), "open": (1000, 1500)}      # src/primitive_forward.py:989-996, 1030-1036
@@ -192,9 +193,6 @@ def outlier_keep_mask(pts, off_h, off_d):
     std = torch.sqrt(dev2.sum(1) / torch.clamp(n_t - 1, min=1))
     std = torch.where(n_t > 1, std, torch.zeros_like(std))
     return valid & (avg < (cloud_mean + 0.5 * std)[seg])
-
-
-KNN3_MAX_POINTS = 10240          # csrc/knn3.hip: 160 values per lane
 
 
 def _mean_dist_broadcast(p, k):

@@ -1,10 +1,12 @@
 """Tensor-level wrappers over the C ABI.  Each function validates layout, allocates
 outputs/workspace through torch's caching allocator and launches on torch's current
 HIP stream.  No arithmetic happens here."""
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, current_stream, ptr, require_cuda
+from .ragged import Clouds
 
 
 def _f32c(t, name):
@@ -84,27 +86,77 @@ def knn(x, k, metric="feature", int32=False):
     return idx
 
 
+KNN3_MAX_POINTS = 10240      # pn_knn3_ragged's limit on the points of one segment in fp32 mode: 160 values per lane
+
+
+# The offsets of a ragged batch.  Every wrapper below takes ``off`` in the form it has always taken — a device int32
+# tensor with ``max_n`` beside it (knn3_ragged, knn3_grid, fps_ragged), or host integers (point_normals and the two
+# orient wrappers) — or the ``ragged.Clouds`` the points were flattened by: its host offsets serve the checks, its
+# device offsets, uploaded once for all the kernels of a call, the launch, and ``max_n`` may be None.
+# The device copy is asked for only where a kernel is launched: a call that returns early or refuses its arguments
+# copies nothing, as before.
+def _device_offsets(who, pts, off, max_n):
+    """What knn3_ragged, knn3_grid and fps_ragged share -> (pts (total,3) fp32 contiguous, upload, S, max_n);
+    ``upload()`` gives the offsets on the device as contiguous int32."""
+    clouds = isinstance(off, Clouds)
+    require_cuda(pts, None if clouds else off)
+    pts = _f32c(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("%s expects (total,3) points, got %s" % (who, tuple(pts.shape),))
+    if clouds:
+        if pts.shape[0] != off.total or pts.device != off.flat.device:
+            raise ValueError("%s: pts %s on %s is not the flat array of the Clouds given as off (%d points on %s)"
+                             % (who, tuple(pts.shape), pts.device, off.total, off.flat.device))
+        return pts, off.device_offsets, off.S, off.max_n if max_n is None else int(max_n)
+    if off.dtype != torch.int32:
+        raise TypeError("off must be int32")
+    return pts, off.contiguous, off.numel() - 1, int(max_n)
+
+
+def _host_view(who, off):
+    """The first thing point_normals and the two orient wrappers do with ``off`` -> (the offsets on the host, the
+    Clouds they came in or None).  A device tensor is a TypeError."""
+    if isinstance(off, Clouds):
+        return off.off, off
+    if torch.is_tensor(off):
+        if off.is_cuda:
+            raise TypeError("%s: off must be host integers (a list, an array or a CPU tensor)" % who)
+        off = off.numpy()
+    return off, None
+
+
+def _host_offsets(who, off, total, k):
+    """The check of the host offsets the same three share (ascending from 0 to total, row * k within int32)
+    -> (offsets int64, S)."""
+    off = np.asarray(off, np.int64).reshape(-1)
+    S = off.shape[0] - 1
+    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+        raise ValueError("%s: off must ascend from 0 to %d" % (who, total))
+    if total * max(k, 3) >= 2 ** 31:
+        raise ValueError("%s: int32 offsets" % who)
+    return off, S
+
+
+def _upload_offsets(off, clouds, dev):
+    """The offsets on ``dev`` as int32: the tensor the Clouds holds, or one stream-ordered copy of host integers."""
+    return clouds.device_offsets() if clouds is not None else _lib.h2d(off.astype(np.int32), dev)
+
+
 def knn3_ragged(pts, off, max_n, k, f64=False, want_dist=False):
     """Neighbours of 3-D points by coordinate differences inside the segments of a ragged batch
     (csrc/knn3.hip; src/fitting_utils.py:150-164, 704-710).  pts (total,3) fp32, off (S+1) int32 device
-    offsets, max_n >= the largest segment (a host integer).  Returns idx (total,k) int32 LOCAL to the
-    segment — nearest first, the point itself first — and, with ``want_dist``, their distances
-    (float64 when ``f64``)."""
-    require_cuda(pts, off)
-    pts = _f32c(pts, "pts")
-    if pts.dim() != 2 or pts.shape[1] != 3:
-        raise ValueError("knn3_ragged expects (total,3) points, got %s" % (tuple(pts.shape),))
-    if off.dtype != torch.int32:
-        raise TypeError("off must be int32")
-    S = off.numel() - 1
+    offsets, max_n >= the largest segment (a host integer) — or off a ``ragged.Clouds`` and max_n None.  Returns idx
+    (total,k) int32 LOCAL to the segment — nearest first, the point itself first — and, with ``want_dist``, their
+    distances (float64 when ``f64``)."""
+    pts, off, S, max_n = _device_offsets("knn3_ragged", pts, off, max_n)
     total = pts.shape[0]
     idx = torch.empty((total, k), dtype=torch.int32, device=pts.device)
     dist = torch.empty((total, k), dtype=torch.float64 if f64 else torch.float32, device=pts.device) if want_dist else None
     if total == 0 or S <= 0:
         return (idx, dist) if want_dist else idx
     with _lib.on_device(pts.device):
-        rc = _lib.load().pn_knn3_ragged(ptr(pts), ptr(off.contiguous()), S, int(max_n), int(k), int(bool(f64)), ptr(idx),
-                                        ptr(dist), current_stream(pts.device))
+        rc = _lib.load().pn_knn3_ragged(ptr(pts), ptr(off()), S, max_n, int(k), int(bool(f64)), ptr(idx), ptr(dist),
+                                        current_stream(pts.device))
     check(rc, "pn_knn3_ragged")
     return (idx, dist) if want_dist else idx
 
@@ -112,19 +164,13 @@ def knn3_ragged(pts, off, max_n, k, f64=False, want_dist=False):
 def knn3_grid(pts, off, max_n, k, want_dist=False):
     """``knn3_ragged``'s fp32 neighbours, bit for bit, by a uniform-grid search (csrc/knn3_grid.hip, definition
     csrc/knn3_grid_math.h): cost O(n k) and no limit on the size of a segment.  pts (total,3) fp32, off (S+1) int32
-    device offsets, max_n >= the largest segment (a host integer).  Returns idx (total,k) int32 LOCAL to the segment —
-    nearest first, the point itself first, equal distances to the smaller index, a segment shorter than k padded with
-    the point itself — and, with ``want_dist``, their fp32 distances.  1 <= k <= 64, total * k < 2^31.  A segment that
-    holds a non-finite coordinate gets the point itself k times and NaN distances.  Five stream-ordered launches on a
-    workspace linear in total, no host synchronisation."""
-    require_cuda(pts, off)
-    pts = _f32c(pts, "pts")
-    if pts.dim() != 2 or pts.shape[1] != 3:
-        raise ValueError("knn3_grid expects (total,3) points, got %s" % (tuple(pts.shape),))
-    if off.dtype != torch.int32:
-        raise TypeError("off must be int32")
+    device offsets, max_n >= the largest segment (a host integer) — or off a ``ragged.Clouds`` and max_n None.  Returns
+    idx (total,k) int32 LOCAL to the segment — nearest first, the point itself first, equal distances to the smaller
+    index, a segment shorter than k padded with the point itself — and, with ``want_dist``, their fp32 distances.
+    1 <= k <= 64, total * k < 2^31.  A segment that holds a non-finite coordinate gets the point itself k times and NaN
+    distances.  Five stream-ordered launches on a workspace linear in total, no host synchronisation."""
+    pts, off, S, max_n = _device_offsets("knn3_grid", pts, off, max_n)
     k = int(k)
-    S = off.numel() - 1
     total = pts.shape[0]
     if total * max(k, 1) >= 2 ** 31:
         raise ValueError("knn3_grid: total * k = %d (below 2^31)" % (total * k))
@@ -136,8 +182,8 @@ def knn3_grid(pts, off, max_n, k, want_dist=False):
     wsz = lib.pn_knn3_grid_workspace_bytes(total, S)
     ws = torch.empty(wsz, dtype=torch.uint8, device=pts.device)
     with _lib.on_device(pts.device):
-        rc = lib.pn_knn3_grid_f32(ptr(pts), ptr(off.contiguous()), S, total, int(max_n), k, ptr(idx), ptr(dist), ptr(ws),
-                                  wsz, current_stream(pts.device))
+        rc = lib.pn_knn3_grid_f32(ptr(pts), ptr(off()), S, total, max_n, k, ptr(idx), ptr(dist), ptr(ws), wsz,
+                                  current_stream(pts.device))
     check(rc, "pn_knn3_grid_f32")
     return (idx, dist) if want_dist else idx
 
@@ -149,17 +195,14 @@ def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
     """k-NN PCA normals of the points of a ragged batch (csrc/normals.hip, arithmetic csrc/normal_math.h): the unit
     eigenvector of the smallest eigenvalue of the covariance of every point's k neighbours.
     pts (total,3) fp32 and idx (total,k) int32 on the GPU, idx the LOCAL indices ``knn3_ragged`` returned; off (S+1):
-    HOST integers (the caller built them) — they are checked here (ascending from 0 to total) and uploaded with the
-    tile table in one stream-ordered copy.  viewpoints (S,3) fp32 on the GPU or None.
+    HOST integers (the caller built them) or a ``ragged.Clouds`` — they are checked here (ascending from 0 to total);
+    host integers are uploaded with the tile table in one stream-ordered copy, a Clouds brings its device offsets and
+    the tile table goes alone.  viewpoints (S,3) fp32 on the GPU or None.
     Returns normals (total,3) fp32 — canonical sign (largest component positive) without viewpoints, else flipped
     towards the segment's viewpoint — and, with ``want_scalars``, (normals, variation (total), gap (total)).
     A neighbourhood of coincident points and a segment of fewer than 3 points give zero normals and scalars."""
-    import numpy as np
     require_cuda(pts, idx, viewpoints)
-    if torch.is_tensor(off):
-        if off.is_cuda:
-            raise TypeError("point_normals: off must be host integers (a list, an array or a CPU tensor)")
-        off = off.numpy()
+    off, clouds = _host_view("point_normals", off)
     pts = _f32c(pts, "pts")
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError("point_normals expects (total,3) points, got %s" % (tuple(pts.shape),))
@@ -171,12 +214,7 @@ def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
         raise TypeError("idx must be int32, got %s" % idx.dtype)
     if tuple(idx.shape) != (total, k):
         raise ValueError("point_normals expects (%d,%d) neighbour indices, got %s" % (total, k, tuple(idx.shape)))
-    off = np.asarray(off, np.int64).reshape(-1)
-    S = off.shape[0] - 1
-    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
-        raise ValueError("point_normals: off must ascend from 0 to %d" % total)
-    if total * max(k, 3) >= 2 ** 31:
-        raise ValueError("point_normals: int32 offsets")
+    off, S = _host_offsets("point_normals", off, total, k)
     dev = pts.device
     if viewpoints is not None:
         viewpoints = _f32c(viewpoints, "viewpoints")
@@ -192,11 +230,14 @@ def point_normals(pts, off, idx, k, viewpoints=None, want_scalars=False):
         ntile = int(tiles.sum())
         tile_seg = np.repeat(np.arange(S), tiles)
         tile_first = off[tile_seg] + (np.arange(ntile) - np.repeat(np.cumsum(tiles) - tiles, tiles)) * tile
-        table = _lib.h2d(np.concatenate([off, tile_seg, tile_first]).astype(np.int32), dev)
+        # host integers ride in front of the tile table, one copy; a Clouds has (or makes) its own
+        ride = [] if clouds is not None else [off]
+        table = _lib.h2d(np.concatenate(ride + [tile_seg, tile_first]).astype(np.int32), dev)
+        off_d, tiles = (clouds.device_offsets(), table) if clouds is not None else (table, table[S + 1:])
         with _lib.on_device(dev):
-            rc = lib.pn_point_normals_f32(ptr(pts), ptr(table), S, total, ptr(idx.contiguous()), k, ptr(viewpoints),
-                                          ptr(table[S + 1:]), ptr(table[S + 1 + ntile:]), ntile, ptr(normals),
-                                          ptr(variation), ptr(gap), current_stream(dev))
+            rc = lib.pn_point_normals_f32(ptr(pts), ptr(off_d), S, total, ptr(idx.contiguous()), k, ptr(viewpoints),
+                                          ptr(tiles), ptr(tiles[ntile:]), ntile, ptr(normals), ptr(variation),
+                                          ptr(gap), current_stream(dev))
         check(rc, "pn_point_normals_f32")
     return (normals, variation, gap) if want_scalars else normals
 
@@ -205,13 +246,10 @@ ORIENT_MIN_K, ORIENT_MAX_K = 1, 64
 
 
 def _orient_args(who, pts, off, idx, k, normals):
-    """The checks ``orient_normals`` and ``orient_normals_global`` share -> (pts, normals, host offsets int64, S, k)."""
-    import numpy as np
+    """The checks ``orient_normals`` and ``orient_normals_global`` share -> (pts, normals, host offsets int64, S, k,
+    the Clouds given as off or None)."""
     require_cuda(pts, idx, normals)
-    if torch.is_tensor(off):
-        if off.is_cuda:
-            raise TypeError("%s: off must be host integers (a list, an array or a CPU tensor)" % who)
-        off = off.numpy()
+    off, clouds = _host_view(who, off)
     pts = _f32c(pts, "pts")
     normals = _f32c(normals, "normals")
     if pts.dim() != 2 or pts.shape[1] != 3:
@@ -226,13 +264,8 @@ def _orient_args(who, pts, off, idx, k, normals):
         raise TypeError("idx must be int32, got %s" % idx.dtype)
     if tuple(idx.shape) != (total, k):
         raise ValueError("%s expects (%d,%d) neighbour indices, got %s" % (who, total, k, tuple(idx.shape)))
-    off = np.asarray(off, np.int64).reshape(-1)
-    S = off.shape[0] - 1
-    if S < 0 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
-        raise ValueError("%s: off must ascend from 0 to %d" % (who, total))
-    if total * max(k, 3) >= 2 ** 31:
-        raise ValueError("%s: int32 offsets" % who)
-    return pts, normals, off, S, k
+    off, S = _host_offsets(who, off, total, k)
+    return pts, normals, off, S, k, clouds
 
 
 def orient_normals(pts, off, idx, k, normals, want_flags=False):
@@ -240,14 +273,13 @@ def orient_normals(pts, off, idx, k, normals, want_flags=False):
     csrc/orient_math.h): signs propagated along the minimum spanning forest of the k-NN graph under 1 - |n_i . n_j|,
     the topmost point of every connected component looking up.
     pts (total,3) fp32, idx (total,k) int32 — the LOCAL indices ``knn3_ragged`` returned — and normals (total,3) fp32
-    on the GPU; off (S+1): HOST integers, checked here (ascending from 0 to total, no segment above
-    ``pn_orient_normals_max_points()``: ValueError) and uploaded in one stream-ordered copy.
+    on the GPU; off (S+1): HOST integers or a ``ragged.Clouds``, checked here (ascending from 0 to total, no segment
+    above ``pn_orient_normals_max_points()``: ValueError); host integers are uploaded in one stream-ordered copy.
     Returns the oriented normals (total,3) — every row the input row, bit-identical or negated — and, with
     ``want_flags``, (normals, flip (total) int32 0/1, seed (total) int32: the local index of the component's seed).
     One launch, no host synchronisation; the same bits from run to run and for every batching.
     ``orient_normals_global`` computes the same on segments of any size."""
-    import numpy as np
-    pts, normals, off, S, k = _orient_args("orient_normals", pts, off, idx, k, normals)
+    pts, normals, off, S, k, clouds = _orient_args("orient_normals", pts, off, idx, k, normals)
     total = pts.shape[0]
     dev = pts.device
     out = torch.empty((total, 3), dtype=torch.float32, device=dev)
@@ -260,9 +292,9 @@ def orient_normals(pts, off, idx, k, normals, want_flags=False):
             raise ValueError("orient_normals: a cloud of %d points; one workgroup orients at most %d points "
                              "(the global-memory engine, orient_normals_global or engine=\"global\" / \"auto\", has no "
                              "limit)" % (int(np.diff(off).max()), limit))
-        table = _lib.h2d(off.astype(np.int32), dev)
+        off_d = _upload_offsets(off, clouds, dev)
         with _lib.on_device(dev):
-            rc = lib.pn_orient_normals_f32(ptr(pts), ptr(table), S, total, ptr(idx.contiguous()), k, ptr(normals),
+            rc = lib.pn_orient_normals_f32(ptr(pts), ptr(off_d), S, total, ptr(idx.contiguous()), k, ptr(normals),
                                            ptr(out), ptr(flip), ptr(seed), current_stream(dev))
         check(rc, "pn_orient_normals_f32")
     return (out, flip, seed) if want_flags else out
@@ -273,8 +305,7 @@ def orient_normals_global(pts, off, idx, k, normals, want_flags=False):
     (csrc/orient_global.hip, steps and schedule csrc/orient_global_math.h).  The same arguments, checks and results,
     without the limit on the points of a segment; total * k < 2^31.  The workspace (linear in total) is allocated
     here; ``pn_orient_normals_global_launches(largest segment)`` stream-ordered launches, no host synchronisation."""
-    import numpy as np
-    pts, normals, off, S, k = _orient_args("orient_normals_global", pts, off, idx, k, normals)
+    pts, normals, off, S, k, clouds = _orient_args("orient_normals_global", pts, off, idx, k, normals)
     total = pts.shape[0]
     dev = pts.device
     out = torch.empty((total, 3), dtype=torch.float32, device=dev)
@@ -284,9 +315,9 @@ def orient_normals_global(pts, off, idx, k, normals, want_flags=False):
         lib = _lib.load()
         wsz = lib.pn_orient_normals_global_workspace_bytes(total, S)
         ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
-        table = _lib.h2d(off.astype(np.int32), dev)
+        off_d = _upload_offsets(off, clouds, dev)
         with _lib.on_device(dev):
-            rc = lib.pn_orient_normals_global_f32(ptr(pts), ptr(table), S, total, int(np.diff(off).max()),
+            rc = lib.pn_orient_normals_global_f32(ptr(pts), ptr(off_d), S, total, int(np.diff(off).max()),
                                                   ptr(idx.contiguous()), k, ptr(normals), ptr(out), ptr(flip),
                                                   ptr(seed), ptr(ws), wsz, current_stream(dev))
         check(rc, "pn_orient_normals_global_f32")
@@ -296,22 +327,18 @@ def orient_normals_global(pts, off, idx, k, normals, want_flags=False):
 def fps_ragged(pts, off, max_n, m, start=None, want_owner=False, want_radius=False):
     """Farthest-point sampling of every segment of a ragged batch (csrc/fps.hip, definition csrc/fps_math.h), exact and
     bit-reproducible.  pts (total,3) fp32, off (S+1) int32 device offsets, max_n >= the largest segment (a host
-    integer), m >= 1 samples per segment, start None (0) or (S,) int32 LOCAL indices (clamped into the segment).
+    integer) — or off a ``ragged.Clouds`` and max_n None —, m >= 1 samples per segment, start None (0) or (S,) int32
+    LOCAL indices (clamped into the segment).
     Returns sample (S,m) int32 LOCAL indices in selection order, -1 past min(m, n) — and, with ``want_owner``, owner
     (total,) int32, the rank of every point's nearest sample, and dist (total,) fp32, the squared distance to it; with
     ``want_radius`` radius (S,m) fp32 last, the distance of every sample to the earlier ones when it was chosen (+inf
     first, NaN where sample is -1).  A segment that holds a non-finite coordinate: -1 and NaN throughout.
     ``pn_fps_launches(m)`` = m + 2 stream-ordered launches on a workspace allocated here, no host synchronisation."""
-    require_cuda(pts, off, start)
-    pts = _f32c(pts, "pts")
-    if pts.dim() != 2 or pts.shape[1] != 3:
-        raise ValueError("fps_ragged expects (total,3) points, got %s" % (tuple(pts.shape),))
-    if off.dtype != torch.int32:
-        raise TypeError("off must be int32")
+    require_cuda(start)
+    pts, off, S, max_n = _device_offsets("fps_ragged", pts, off, max_n)
     m = int(m)
     if m < 1:
         raise ValueError("fps_ragged: m = %d (m >= 1)" % m)
-    S = off.numel() - 1
     total = pts.shape[0]
     if total >= 2 ** 31:
         raise ValueError("fps_ragged: total = %d (below 2^31)" % total)
@@ -331,8 +358,8 @@ def fps_ragged(pts, off, max_n, m, start=None, want_owner=False, want_radius=Fal
         wsz = lib.pn_fps_workspace_bytes(total, S, m)
         ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            rc = lib.pn_fps_f32(ptr(pts), ptr(off.contiguous()), S, total, int(max_n), m, ptr(start), ptr(sample),
-                                ptr(radius), ptr(owner), ptr(dist), ptr(ws), wsz, current_stream(dev))
+            rc = lib.pn_fps_f32(ptr(pts), ptr(off()), S, total, max_n, m, ptr(start), ptr(sample), ptr(radius),
+                                ptr(owner), ptr(dist), ptr(ws), wsz, current_stream(dev))
         check(rc, "pn_fps_f32")
     out = (sample,) + ((owner, dist) if want_owner else ()) + ((radius,) if want_radius else ())
     return out if len(out) > 1 else sample

@@ -18,13 +18,12 @@ from global memory over many workgroups (csrc/orient_global.hip: a fixed, stream
 rounds), the same bits on clouds of any size — a raw scan is
 ``estimate_normals(pts, orient="mst", search="auto", engine="auto")``.  The method's known weakness stays: the tree can
 cross a sharp crease or a thin wall with the wrong sign, and an open patch gets a consistent but arbitrary side."""
-import numpy as np
 import torch
 
 from . import _lib
 from . import kernels as K
-
-KNN3_MAX_POINTS = 10240      # pn_knn3_ragged's limit on the points of one segment (fp32 mode)
+from .kernels import KNN3_MAX_POINTS
+from .ragged import Clouds
 
 
 def _viewpoints(viewpoint, S, device):
@@ -46,33 +45,6 @@ def _viewpoints(viewpoint, S, device):
     if tuple(viewpoint.shape) != (S, 3):
         raise ValueError("estimate_normals: viewpoint must be (3,) or (%d,3), got %s" % (S, tuple(viewpoint.shape)))
     return viewpoint.to(device).contiguous()
-
-
-def _clouds(points, who, what="points"):
-    """(N,3), (B,N,3) or a list of (N_b,3) fp32 tensors on the GPU -> (layout, sizes, flat (total,3)); layout is
-    "single", "list" or the shape (B, N) of a batch."""
-    if isinstance(points, (list, tuple)):
-        clouds = list(points)
-        if not clouds:
-            raise ValueError("%s: an empty list of clouds" % who)
-        if not all(torch.is_tensor(c) for c in clouds):
-            raise TypeError("%s: a list of clouds holds tensors" % who)
-        layout = "list"
-    elif torch.is_tensor(points):
-        clouds = [points]
-        layout = "single" if points.dim() == 2 else "batch"
-    else:
-        raise TypeError("%s: %s must be a tensor or a list of tensors" % (who, what))
-    _lib.require_cuda(*clouds)
-    for c in clouds:
-        if c.dtype != torch.float32:
-            raise ValueError("%s: %s must be float32, got %s" % (who, what, c.dtype))
-        if c.dim() != (3 if layout == "batch" else 2) or c.shape[-1] != 3:
-            raise ValueError("%s: %s must be (N,3), (B,N,3) or a list of (N,3), got %s" % (who, what, tuple(c.shape)))
-    if layout == "batch":
-        B, N = points.shape[:2]
-        return (B, N), [N] * B, points.reshape(B * N, 3)
-    return layout, [c.shape[0] for c in clouds], clouds[0] if len(clouds) == 1 else torch.cat(clouds)
 
 
 def _search(search, sizes, who):
@@ -100,23 +72,11 @@ def _engine(engine, sizes):
     return K.orient_normals_global if engine == "global" else K.orient_normals
 
 
-def _neighbours(flat, sizes, k, search="brute"):
-    """One neighbour search over the ragged batch: (host offsets (S+1) int64, idx (total,k) int32)."""
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    if int(off[-1]) == 0:
-        return off, torch.empty((0, k), dtype=torch.int32, device=flat.device)
-    knn3 = K.knn3_grid if search == "grid" else K.knn3_ragged
-    return off, knn3(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), k)
-
-
-def _shaped(out, layout, sizes):
-    """(total,3) and (total,) results back in the layout of the input."""
-    if isinstance(layout, tuple):
-        B, N = layout
-        return tuple(o.reshape(B, N, 3) if o.dim() == 2 else o.reshape(B, N) for o in out)
-    if layout == "list":
-        return tuple(list(torch.split(o, sizes)) for o in out)
-    return tuple(out)
+def _neighbours(clouds, k, search="brute"):
+    """One neighbour search over the ragged batch: idx (total,k) int32."""
+    if clouds.total == 0:
+        return torch.empty((0, k), dtype=torch.int32, device=clouds.flat.device)
+    return (K.knn3_grid if search == "grid" else K.knn3_ragged)(clouds.flat, clouds, None, k)
 
 
 def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=None, search=None, engine=None):
@@ -150,20 +110,20 @@ def estimate_normals(points, k=16, viewpoint=None, return_scalars=False, orient=
     if engine is not None and orient is None:
         raise ValueError("estimate_normals: engine=%r without orient=\"mst\" (the engine is the orientation's)"
                          % (engine,))
-    layout, sizes, flat = _clouds(points, "estimate_normals")
+    clouds = Clouds(points, "estimate_normals")
     k = int(k)
     if not K.NORMALS_MIN_K <= k <= K.NORMALS_MAX_K:
         raise ValueError("estimate_normals: k must be %d .. %d, got %d" % (K.NORMALS_MIN_K, K.NORMALS_MAX_K, k))
-    search = _search(search, sizes, "estimate_normals")
-    orienter = _engine(engine, sizes) if orient == "mst" else None
-    view = _viewpoints(viewpoint, len(sizes), flat.device)
-    off, idx = _neighbours(flat, sizes, k, search)
-    out = K.point_normals(flat, off, idx, k, viewpoints=view, want_scalars=return_scalars)
+    search = _search(search, clouds.sizes, "estimate_normals")
+    orienter = _engine(engine, clouds.sizes) if orient == "mst" else None
+    view = _viewpoints(viewpoint, clouds.S, clouds.flat.device)
+    idx = _neighbours(clouds, k, search)
+    out = K.point_normals(clouds.flat, clouds, idx, k, viewpoints=view, want_scalars=return_scalars)
     out = out if return_scalars else (out,)
     if orient == "mst":
-        out = (orienter(flat, off, idx, k, out[0]),) + tuple(out[1:])
-    out = _shaped(out, layout, sizes)
-    return tuple(out) if return_scalars else out[0]
+        out = (orienter(clouds.flat, clouds, idx, k, out[0]),) + tuple(out[1:])
+    out = tuple(clouds.per_point(o) for o in out)
+    return out if return_scalars else out[0]
 
 
 def orient_normals(points, normals, k=16, return_flags=False, search=None, engine=None):
@@ -188,16 +148,18 @@ def orient_normals(points, normals, k=16, return_flags=False, search=None, engin
        one-workgroup kernel when every cloud has at most 10 240 points, the global engine for the whole call
        otherwise.  The result never depends on the engine."""
     _check_engine(engine, "orient_normals")
-    layout, sizes, flat = _clouds(points, "orient_normals")
-    n_layout, n_sizes, n_flat = _clouds(normals, "orient_normals", "normals")
-    if (n_layout, n_sizes) != (layout, sizes):
-        raise ValueError("orient_normals: points and normals must have the same layout and sizes")
+    clouds = Clouds(points, "orient_normals")
+    n_flat = clouds.beside(normals, "orient_normals", "normals")
+    if n_flat.dtype != torch.float32:
+        raise ValueError("orient_normals: normals must be float32, got %s" % n_flat.dtype)
+    if tuple(n_flat.shape[1:]) != (3,):
+        raise ValueError("orient_normals: normals must be (N,3), (B,N,3) or a list of (N,3), got rows of %s"
+                         % (tuple(n_flat.shape[1:]),))
     k = int(k)
     if not K.ORIENT_MIN_K <= k <= K.ORIENT_MAX_K:
         raise ValueError("orient_normals: k must be %d .. %d, got %d" % (K.ORIENT_MIN_K, K.ORIENT_MAX_K, k))
-    search = _search(search, sizes, "orient_normals")
-    orienter = _engine(engine, sizes)
-    off, idx = _neighbours(flat, sizes, k, search)
-    out = orienter(flat, off, idx, k, n_flat, want_flags=return_flags)
-    out = _shaped(out if return_flags else (out,), layout, sizes)
-    return tuple(out) if return_flags else out[0]
+    search = _search(search, clouds.sizes, "orient_normals")
+    orienter = _engine(engine, clouds.sizes)
+    idx = _neighbours(clouds, k, search)
+    out = orienter(clouds.flat, clouds, idx, k, n_flat, want_flags=return_flags)
+    return tuple(clouds.per_point(o) for o in out) if return_flags else clouds.per_point(out)

@@ -23,15 +23,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
-from .point_normals import _clouds, _shaped
-
-
-def _flat_clouds(points, who):
-    """_clouds with this module's errors: a non-fp32 dtype is a TypeError."""
-    for c in (points if isinstance(points, (list, tuple)) else [points]):
-        if torch.is_tensor(c) and c.is_cuda and c.dtype != torch.float32:
-            raise TypeError("%s: points must be float32, got %s" % (who, c.dtype))
-    return _clouds(points, who)
+from .ragged import Clouds
 
 
 def _starts(start, S, device, who):
@@ -52,23 +44,17 @@ def _starts(start, S, device, who):
 
 
 def _samples(points, m, start, who, want_owner, want_radius, full=False):
+    """The clouds as a ``Clouds`` (a non-fp32 dtype is a TypeError here) and the tuple ``K.fps_ragged`` returns."""
     if isinstance(m, bool) or not isinstance(m, numbers.Integral) or m < 1:
         raise ValueError("%s: m must be an integer >= 1, got %r" % (who, m))
-    layout, sizes, flat = _flat_clouds(points, who)
-    if full and min(sizes) < m:
-        raise ValueError("%s: a cloud of %d points cannot give m = %d samples" % (who, min(sizes), m))
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    start = _starts(start, len(sizes), flat.device, who)
-    out = K.fps_ragged(flat, _lib.h2d(off.astype(np.int32), flat.device), max(sizes), int(m), start=start,
-                       want_owner=want_owner, want_radius=want_radius)
-    return layout, sizes, flat, off, (out if isinstance(out, tuple) else (out,))
-
-
-def _per_cloud(rows, layout):
-    """(S,m,...) results back in the layout of the input."""
-    if isinstance(layout, tuple):
-        return rows
-    return list(rows.unbind(0)) if layout == "list" else rows[0]
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    if clouds.S == 0:
+        raise ValueError("%s: an empty batch of clouds" % who)
+    if full and min(clouds.sizes) < m:
+        raise ValueError("%s: a cloud of %d points cannot give m = %d samples" % (who, min(clouds.sizes), m))
+    start = _starts(start, clouds.S, clouds.flat.device, who)
+    out = K.fps_ragged(clouds.flat, clouds, None, int(m), start=start, want_owner=want_owner, want_radius=want_radius)
+    return clouds, (out if isinstance(out, tuple) else (out,))
 
 
 def farthest_point_sample(points, m, start=None, return_owner=False, return_radius=False):
@@ -86,12 +72,12 @@ def farthest_point_sample(points, m, start=None, return_owner=False, return_radi
     A cloud that holds a non-finite coordinate gets -1 and NaN throughout.  All results are functions of the input
     alone.  m + 2 stream-ordered launches, no host synchronisation."""
     who = "farthest_point_sample"
-    layout, sizes, _, _, out = _samples(points, m, start, who, return_owner, return_radius)
-    res = [_per_cloud(out[0].long(), layout)]
+    clouds, out = _samples(points, m, start, who, return_owner, return_radius)
+    res = [clouds.per_cloud(out[0].long())]
     if return_owner:
-        res += list(_shaped((out[1].long(), out[2]), layout, sizes))
+        res += [clouds.per_point(out[1].long()), clouds.per_point(out[2])]
     if return_radius:
-        res.append(_per_cloud(out[-1], layout))
+        res.append(clouds.per_cloud(out[-1]))
     return tuple(res) if len(res) > 1 else res[0]
 
 
@@ -103,26 +89,12 @@ def reduce_cloud(points, m, *per_point, start=None):
     (m,...), (B,m,...) or lists of (m,...); ``owner`` as in ``farthest_point_sample`` — keep it for ``lift``.
     Raises ValueError if a cloud has fewer than m points (a -1 index would gather the wrong row silently)."""
     who = "reduce_cloud"
-    layout, sizes, flat, off, out = _samples(points, m, start, who, True, False, full=True)
-    S = len(sizes)
-    rows = (out[0].long() + _lib.h2d(off[:-1], flat.device)[:, None]).reshape(-1)      # rows of the flat arrays
+    clouds, out = _samples(points, m, start, who, True, False, full=True)
+    rows = (out[0] + clouds.device_offsets()[:-1, None]).long().reshape(-1)            # rows of the flat arrays
     res = []
-    for a in (points,) + per_point:
-        if isinstance(a, (list, tuple)):
-            if layout != "list" or [int(x.shape[0]) for x in a] != sizes:
-                raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
-            a = a[0] if len(a) == 1 else torch.cat(list(a))
-        elif not torch.is_tensor(a):
-            raise TypeError("%s: a per-point array must be a tensor or a list of tensors" % who)
-        elif isinstance(layout, tuple):
-            if tuple(a.shape[:2]) != layout:
-                raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
-            a = a.reshape((-1,) + tuple(a.shape[2:]))
-        elif layout != "single" or a.shape[0] != sizes[0]:
-            raise ValueError("%s: a per-point array must have the layout and the sizes of the points" % who)
-        _lib.require_cuda(a)
-        res.append(_per_cloud(a[rows].reshape((S, int(m)) + tuple(a.shape[1:])), layout))
-    return tuple(res) + (_shaped((out[1].long(),), layout, sizes)[0],)
+    for a in (clouds.flat,) + tuple(clouds.beside(a, who, "a per-point array") for a in per_point):
+        res.append(clouds.per_cloud(a[rows].reshape((clouds.S, int(m)) + tuple(a.shape[1:]))))
+    return tuple(res) + (clouds.per_point(out[1].long()),)
 
 
 def lift(values, owner):

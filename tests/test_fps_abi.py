@@ -4,16 +4,16 @@ decoding of the slots) against ``fps_numpy``, an independent numpy restatement o
 argmax that takes the first maximum) — every output exactly equal, in both tile orders —, the three exact properties
 of the definition, the stand-alone program, the export of csrc/fps.hip and its argument checks."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.helpers import native
+from tests.helpers.native import ROOT      # noqa: F401  (tests/test_fps_gpu.py takes it from here)
 from tests.test_knn3_grid_abi import collinear, copies_among_random, lattice, offset_cloud, planar
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "native", "fps_host.cpp")
+SOURCE = native.source("fps_host.cpp")
 NAMES = ("pn_fps_f32", "pn_fps_workspace_bytes", "pn_fps_launches")
 TILE = 1024      # FPS_TILE of csrc/fps_math.h (test_the_tile_is_the_one_the_tests_assume)
 
@@ -97,15 +97,9 @@ def clouds():
 # ---------------------------------------------------------------------------------------------
 # the host-compiled header
 # ---------------------------------------------------------------------------------------------
-def build_harness(directory):
-    out = os.path.join(str(directory), "libfph.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
-    return ctypes.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return build_harness(tmp_path_factory.mktemp("fph"))
+    return native.build_harness(tmp_path_factory.mktemp("fph"), "fph", SOURCE)
 
 
 def host_fps(lib, batch, m, start=None, order=0):
@@ -182,8 +176,7 @@ def test_a_ragged_batch_with_empty_short_and_non_finite_clouds(harness):
 
 
 def test_the_program_checks_itself_and_reads_a_file(harness, tmp_path):
-    exe = str(tmp_path / "fps_host")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
+    exe = native.build_program(tmp_path, "fps_host", SOURCE)
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and "0 differences" in run.stdout, run.stdout
     P, m = offset_cloud(150), 12
@@ -197,15 +190,7 @@ def test_the_program_checks_itself_and_reads_a_file(harness, tmp_path):
 # the export and the argument checks, which run before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def load_raw():
-    """The library through a private ctypes handle, the entry points bound from the header's table."""
-    from parsenet_codebase_amd import _lib
-    _lib.load()
-    handle = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES + ("pn_abi_version",):
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    handle.pn_last_error.restype = ctypes.c_char_p
-    return handle
+    return native.load_raw(NAMES)
 
 
 @pytest.fixture(scope="module")

@@ -11,10 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import native
+from tests.helpers.native import ROOT
 from tests.test_point_normals_abi import knn3
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "native", "knn3_grid_host.cpp")
+SOURCE = native.source("knn3_grid_host.cpp")
 NAME = "pn_knn3_grid_f32"
 WORKSPACE = "pn_knn3_grid_workspace_bytes"
 PPCS = (1, 4, 64)      # points per cell: 1 makes many rings, 64 few cells, 4 is the library's own value
@@ -100,17 +101,11 @@ def adversarial(scale=1):
 # ---------------------------------------------------------------------------------------------
 # the host-compiled header
 # ---------------------------------------------------------------------------------------------
-def build_harness(directory):
-    out = os.path.join(str(directory), "libkgh.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
-    lib = ctypes.CDLL(out)
-    lib.kgh_bound_violations.restype = ctypes.c_longlong
-    return lib
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return build_harness(tmp_path_factory.mktemp("kgh"))
+    lib = native.build_harness(tmp_path_factory.mktemp("kgh"), "kgh", SOURCE)
+    lib.kgh_bound_violations.restype = ctypes.c_longlong
+    return lib
 
 
 def _p(a):
@@ -227,8 +222,7 @@ def test_a_non_finite_coordinate_gives_self_rows_and_nan_distances(harness):
 
 
 def test_the_program_reads_a_cloud_from_stdin_and_a_file(harness, tmp_path):
-    exe = str(tmp_path / "knn3_grid_host")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
+    exe = native.build_program(tmp_path, "knn3_grid_host", SOURCE)
     P, k = tight_pairs(150, 1), 7
     text = "%d %d %d\n" % (P.shape[0], k, 2) + "".join("%.9g %.9g %.9g\n" % tuple(p) for p in P)
     path = tmp_path / "cloud.txt"
@@ -244,15 +238,7 @@ def test_the_program_reads_a_cloud_from_stdin_and_a_file(harness, tmp_path):
 # the export and the argument checks, which run before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def load_raw():
-    """The library through a private ctypes handle, the two entry points bound from the header's table."""
-    from parsenet_codebase_amd import _lib
-    _lib.load()
-    handle = ctypes.CDLL(_lib.LIB_PATH)
-    for name in (NAME, WORKSPACE, "pn_abi_version"):
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    handle.pn_last_error.restype = ctypes.c_char_p
-    return handle
+    return native.load_raw((NAME, WORKSPACE))
 
 
 @pytest.fixture(scope="module")

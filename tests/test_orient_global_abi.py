@@ -13,12 +13,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import native
+from tests.helpers.native import ROOT
 from tests.test_orient_normals_abi import (UP, build_harness, canonical_normals, closed_shapes, host_orient, lattice,
                                            py_weights, same_bits, torus)
 from tests.test_point_normals_abi import knn3, sphere
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "native", "orient_global_host.cpp")
+SOURCE = native.source("orient_global_host.cpp")
 STEPS = os.path.join(ROOT, "parsenet_codebase_amd", "csrc", "orient_global_math.h")
 NAME = "pn_orient_normals_global_f32"
 ARGS = ("pts", "off", "S", "total", "max_n", "idx", "k", "normals_in", "normals_out", "flip", "seed", "ws", "ws_bytes",
@@ -95,9 +96,7 @@ def big_torus():
 # the host simulation
 # ---------------------------------------------------------------------------------------------
 def build_simulation(directory):
-    out = os.path.join(str(directory), "libogh.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
-    return ctypes.CDLL(out)
+    return native.build_harness(directory, "ogh", SOURCE)
 
 
 @pytest.fixture(scope="module")
@@ -252,10 +251,8 @@ def test_large_closed_shapes(harness, simulation, large_shapes):
 
 
 def test_the_program_reads_a_cloud_and_reports(tmp_path):
-    exe, oracle = str(tmp_path / "orient_global_host"), str(tmp_path / "orient_math_host")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", oracle,
-                    os.path.join(ROOT, "tests", "native", "orient_math_host.cpp")], check=True)
+    exe = native.build_program(tmp_path, "orient_global_host", SOURCE)
+    oracle = native.build_program(tmp_path, "orient_math_host", native.source("orient_math_host.cpp"))
     P, _ = torus(nu=16, nv=9)
     k = 6
     idx = knn3(P, k)
@@ -277,15 +274,8 @@ def test_the_program_reads_a_cloud_and_reports(tmp_path):
 # the exports and the argument checks, which run before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def load_raw():
-    """The library through a private ctypes handle, the entry points bound from the header's table."""
-    from parsenet_codebase_amd import _lib, build
-    handle = ctypes.CDLL(build.build(verbose=False))
-    for name in (NAME, "pn_orient_normals_global_workspace_bytes", "pn_orient_normals_global_launches",
-                 "pn_orient_normals_max_points", "pn_abi_version"):
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    handle.pn_last_error.restype = ctypes.c_char_p
-    return handle
+    return native.load_raw((NAME, "pn_orient_normals_global_workspace_bytes", "pn_orient_normals_global_launches",
+                            "pn_orient_normals_max_points"))
 
 
 @pytest.fixture(scope="module")

@@ -11,10 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import native
+from tests.helpers.native import ROOT
 from tests.test_point_normals_abi import knn3, reference, sphere
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "native", "orient_math_host.cpp")
+SOURCE = native.source("orient_math_host.cpp")
 NAME = "pn_orient_normals_f32"
 ARGS = ("pts", "off", "S", "total", "idx", "k", "normals_in", "normals_out", "flip", "seed", "stream")
 
@@ -133,9 +134,7 @@ def py_orient(P, idx, normals):
 # the host-compiled restatement
 # ---------------------------------------------------------------------------------------------
 def build_harness(directory):
-    out = os.path.join(str(directory), "libomh.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
-    lib = ctypes.CDLL(out)
+    lib = native.build_harness(directory, "omh", SOURCE)
     lib.omh_weight.restype = ctypes.c_float
     lib.omh_weight.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.omh_key.restype = lib.omh_zkey.restype = ctypes.c_ulonglong
@@ -349,8 +348,7 @@ def test_zero_normals_and_a_level_seed(harness):
 
 
 def test_the_program_reads_a_cloud_from_stdin_and_a_file(harness, tmp_path):
-    exe = str(tmp_path / "orient_math_host")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
+    exe = native.build_program(tmp_path, "orient_math_host", SOURCE)
     P, _ = torus(nu=16, nv=9)
     k = 6
     idx = knn3(P, k)
@@ -374,14 +372,7 @@ def test_the_program_reads_a_cloud_from_stdin_and_a_file(harness, tmp_path):
 # the export and the argument checks, which run before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def load_raw():
-    """The library through a private ctypes handle, the two entry points bound from the header's table."""
-    from parsenet_codebase_amd import _lib, build
-    handle = ctypes.CDLL(build.build(verbose=False))
-    for name in (NAME, "pn_orient_normals_max_points", "pn_abi_version"):
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    handle.pn_last_error.restype = ctypes.c_char_p
-    return handle
+    return native.load_raw((NAME, "pn_orient_normals_max_points"))
 
 
 @pytest.fixture(scope="module")

@@ -9,8 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "native", "normal_math_host.cpp")
+from tests.helpers import native
+from tests.helpers.native import ROOT
+
+SOURCE = native.source("normal_math_host.cpp")
 NAME = "pn_point_normals_f32"
 KS = (3, 5, 16, 64)
 
@@ -149,9 +151,7 @@ def segment_reference(clouds, k):
 # the host-compiled header
 # ---------------------------------------------------------------------------------------------
 def build_harness(directory):
-    out = os.path.join(str(directory), "libnmh.so")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", out, SOURCE], check=True)
-    lib = ctypes.CDLL(out)
+    lib = native.build_harness(directory, "nmh", SOURCE)
     lib.nmh_sweeps.restype = ctypes.c_int
     return lib
 
@@ -338,8 +338,7 @@ def test_viewpoint_flip(harness):
 
 
 def test_the_program_reads_neighbourhoods_from_stdin_and_a_file(harness, tmp_path):
-    exe = str(tmp_path / "normal_math_host")
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-o", exe, SOURCE], check=True)
+    exe = native.build_program(tmp_path, "normal_math_host", SOURCE)
     P, k = wavy_grid(), 5
     idx = knn3(P, k)
     text = "%d %d\n" % (P.shape[0], k) + "".join("%.9g %.9g %.9g\n" % tuple(p) for p in P)
@@ -358,14 +357,7 @@ def test_the_program_reads_neighbourhoods_from_stdin_and_a_file(harness, tmp_pat
 # the export and the argument checks, which run before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def load_raw():
-    """The library through a private ctypes handle, the two entry points bound from the header's table."""
-    from parsenet_codebase_amd import _lib, build
-    handle = ctypes.CDLL(build.build(verbose=False))
-    for name in (NAME, "pn_point_normals_tile"):
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    handle.pn_last_error.restype = ctypes.c_char_p
-    return handle
+    return native.load_raw((NAME, "pn_point_normals_tile"))
 
 
 @pytest.fixture(scope="module")
