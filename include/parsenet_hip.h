@@ -923,6 +923,32 @@ int pn_fps_launches(int m);
 int pn_fps_f32(const float* pts, const int* off, int S, int total, int max_n, int m, const int32_t* start,
                int32_t* sample, float* radius, int32_t* owner, float* dist, void* ws, long long ws_bytes, void* stream);
 
+/* ---- statistical outlier removal on clouds of any size (csrc/outlier.hip, definition: csrc/outlier_math.h) ----------
+ * dist (total,k) fp32: the neighbour distances pn_knn3_ragged (fp32 mode) or pn_knn3_grid_f32 wrote — nearest first, the
+ * point itself first, padded with the point itself in a segment shorter than k; off (S+1) DEVICE int32 row offsets from
+ * 0 to total; 1 <= k <= 64; std_ratio finite and >= 0.  Per segment of n points, k_c = min(k, n), under the definition
+ * of csrc/outlier_math.h: avg (total) fp64, a_i = the sum of the k_c distances in ascending order / k_c; stats (S,3)
+ * fp64: mean = SUM(a_i > 0 ? a_i : 0) / n, std = sqrt(SUM(a_i > 0 ? (a_i - mean)^2 : 0) / (n - 1)) (0 for n <= 1) and
+ * thr = mean + std_ratio * std, SUM being one fixed tree over tiles of 1 024 points of the segment; keep (total) 0/1:
+ * a_i > 0 && a_i < thr; kept (S) int32: the kept points of the segment; index (total) int32 or NULL: the LOCAL indices
+ * of the kept points ascending in the first kept[s] entries of the segment's rows, -1 behind them.  A NaN a_i enters
+ * the sums as NaN and then replaces every a_i of its segment: a segment that holds a non-finite coordinate (some or all
+ * of its rows of dist NaN) ends with avg, mean, std and thr NaN, keep 0 and kept 0.  An empty segment: mean and thr NaN, std 0, kept 0.  A row that no valid segment of off holds gets
+ * avg NaN, keep 0 and index -1; a segment that does not lie inside 0 .. total gets NaN stats and kept 0.  All outputs
+ * are functions of dist, the offsets of the segment's own rows, k and std_ratio alone: the same bits from run to run
+ * and for every batching.
+ * pn_outlier_launches() = 6 stream-ordered kernel launches, each over all segments; it needs no GPU.  No host
+ * synchronisation, no cooperative launch, no waiting between workgroups, no atomics.  Workspace of
+ * pn_outlier_workspace_bytes(total, S) bytes: 20 (total / 1024 + S) + 16.
+ * PN_ERR_ARG (before any launch) for k < 1 or k > 64, S < 0, total < 0, total * k >= 2^31, a negative or non-finite
+ * std_ratio, a NULL dist, off, avg, stats, keep, kept or ws, or a workspace that is too small; total == 0 or S == 0
+ * returns 0 without a launch and writes nothing. */
+long long pn_outlier_workspace_bytes(long long total, int S);
+int pn_outlier_launches(void);
+int pn_outlier_stat_f32(const float* dist, const int* off, int S, int total, int k, double std_ratio, double* avg,
+                        double* stats, uint8_t* keep, int32_t* kept, int32_t* index, void* ws, long long ws_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,143 @@
+"""Take the stray points out of a raw scan before anything else looks at it: statistical outlier removal on the GPU.
+
+A scan with a handful of stray points spends its first farthest-point samples on the strays, the PCA normals next to a
+stray are garbage, and the spanning-tree orientation can bridge through one.  ``outlier_statistic`` is open3d's
+``remove_statistical_outlier``: a point is kept if the mean distance to its k nearest neighbours (itself included) is
+positive and below mean + std_ratio * std of that statistic over its cloud.  ``remove_outliers`` applies it to the points
+and to every array that runs beside them, and ``restore`` carries per-kept-point results back to the scan.
+
+    pts, nrm, index = remove_outliers(scan, normals, search="auto")      # before everything else
+    red, nrm_r, owner = reduce_cloud(pts, 10000, nrm)                    # sampling.py
+    # network on red
+    labels = restore(lift(labels_r, owner), index, n, -1)                # back to the n scanned points, strays -1
+
+The definition (csrc/outlier_math.h) is exact and bit-reproducible: the fp32 neighbour distances of ``knn3_ragged`` /
+``knn3_grid`` (the same bits from both), summed in fp64 in ascending order, and the two sums over a cloud taken by one
+fixed tree that depends on the cloud alone.  csrc/outlier.hip runs it in six stream-ordered launches over the whole
+ragged batch, without atomics, on clouds of any size.
+
+Limits.  The statistic is global per cloud: a scan whose density varies strongly (a near and a far surface in one
+cloud) loses the sparse part first.  The distances are fp32, so a point whose statistic lies within about 1e-6 relative
+of the threshold may fall on the other side than with open3d's fp64 distances.  ``fitting_eval.outlier_keep_mask`` (the
+fixed (20, 0.5) filter of the evaluation-mode spline segments, on fp64 distances) is a different tool and stays."""
+import math
+import numbers
+
+import torch
+
+from . import _lib
+from . import kernels as K
+from .point_normals import _search
+from .ragged import Clouds
+
+
+def _arguments(k, std_ratio, who):
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not K.OUTLIER_MIN_K <= k <= K.OUTLIER_MAX_K:
+        raise ValueError("%s: k must be an integer %d .. %d, got %r" % (who, K.OUTLIER_MIN_K, K.OUTLIER_MAX_K, k))
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, numbers.Real) or not (
+            0.0 <= std_ratio and math.isfinite(std_ratio)):
+        raise ValueError("%s: std_ratio must be a finite number >= 0, got %r" % (who, std_ratio))
+    return int(k), float(std_ratio)
+
+
+def _statistic(clouds, k, std_ratio, search, who, want_index):
+    """One neighbour search and one ``K.outlier_stat`` call on checked arguments -> what ``outlier_stat`` returned."""
+    search = _search(search, clouds.sizes, who)
+    if clouds.total == 0:
+        dist = torch.empty((0, k), dtype=torch.float32, device=clouds.flat.device)
+    else:
+        dist = (K.knn3_grid if search == "grid" else K.knn3_ragged)(clouds.flat, clouds, None, k, want_dist=True)[1]
+    return K.outlier_stat(dist, clouds, k, std_ratio, want_index=want_index)
+
+
+def outlier_statistic(points, k=20, std_ratio=2.0, search=None, return_stats=False):
+    """Which points of every cloud are no statistical outliers.
+
+    points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
+    k: neighbours per point, the point itself included, an integer 1 .. 64 (open3d's nb_neighbors).  A cloud of fewer
+       than k points uses all of its points.
+    std_ratio: a finite number >= 0: the threshold is mean + std_ratio * std of the statistic over the cloud.
+    search: None, "grid" or "auto", the neighbour search as in ``estimate_normals`` (None: at most 10 240 points per
+       cloud, a ValueError above).  The result never depends on it.
+    Returns ``keep``, a bool mask in the layout of the points: (N,), (B,N) or a list of (N_b,).  With ``return_stats``
+    a tuple (keep, a, stats): a, fp64 in the layout of the points, the mean distance of every point to its min(k, n)
+    nearest; stats fp64, (3,), (B,3) or a list of (3,): mean, std and threshold of the cloud.  A point is kept iff
+    0 < a < threshold: a point whose k nearest coincide with it is not kept (as in open3d), and a cloud of one point, or
+    one whose statistic is the same everywhere, keeps nothing.  A cloud that holds a non-finite coordinate: a and stats
+    NaN, nothing kept.  All results are functions of the cloud alone, whatever the batch.
+    One neighbour search and one ``kernels.outlier_stat`` call (six launches), no host synchronisation."""
+    who = "outlier_statistic"
+    k, std_ratio = _arguments(k, std_ratio, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    a, stats, keep, _ = _statistic(clouds, k, std_ratio, search, who, False)
+    keep = clouds.per_point(keep)
+    return (keep, clouds.per_point(a), clouds.per_cloud(stats)) if return_stats else keep
+
+
+def remove_outliers(points, *per_point, k=20, std_ratio=2.0, search=None):
+    """The one call in front of everything else: (points[index], *[a[index] for a in per_point], index).
+
+    points, k, std_ratio, search: as in ``outlier_statistic``.  per_point: arrays with one row per point (normals,
+    colours, labels) in the layout of ``points``: (N,...), (B,N,...) or lists of (N_b,...).
+    ``index``, int64, holds per cloud the original row of every kept point, ascending — keep it for ``restore``.  A
+    single cloud comes back as tensors; a batch or a list comes back as LISTS of tensors, one per cloud, because the
+    clouds now differ in size.  A cloud may come back empty.
+    Exactly one host read: the kept counts of the clouds, which size the results."""
+    who = "remove_outliers"
+    k, std_ratio = _arguments(k, std_ratio, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    beside = tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    _, _, _, kept, index = _statistic(clouds, k, std_ratio, search, who, True)
+    counts = _read_counts(kept)
+    base = clouds.off[:-1].tolist()
+    local = [index[o:o + m].long() for o, m in zip(base, counts)]                  # ascending rows of every cloud
+    rows = [i + o for i, o in zip(local, base)]                                    # ... and of the flat arrays
+    rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+    res = [a[rows] if clouds.layout == "single" else list(torch.split(a[rows], counts))
+           for a in (clouds.flat,) + beside]
+    return tuple(res) + (local[0] if clouds.layout == "single" else local,)
+
+
+def _read_counts(kept):
+    """The (S,) int32 kept counts on the host as a list: one stream-ordered download into pinned memory, one wait."""
+    host, slot = _lib.pinned_like(kept.shape, kept.dtype, hold=True)
+    try:
+        host.copy_(kept, non_blocking=True)
+        if slot is not None:
+            _lib._PinnedRing.arm(slot)
+            _lib.wait_event(slot["event"])
+        else:
+            torch.cuda.current_stream(kept.device).synchronize()
+        return [int(c) for c in host.tolist()]
+    finally:
+        _lib._PinnedRing.release(slot)
+
+
+def restore(values, index, n, fill):
+    """Per-kept-point values back to the n points of the scan: out[index] = values, ``fill`` everywhere else.
+
+    values: (kept,...) — labels, ``lift``ed results, anything with one row per kept point —, index: (kept,) int64 as
+    ``remove_outliers`` returned it, n: the points of the scan; or lists of as many tensors, n an int or one int per
+    cloud.  Returns (n,...) in the dtype of ``values``, or a list.  Raises ValueError for an index outside 0 .. n - 1
+    (one host read per cloud)."""
+    if isinstance(index, (list, tuple)):
+        if not isinstance(values, (list, tuple)) or len(values) != len(index):
+            raise ValueError("restore: a list of indices takes a list of as many value tensors")
+        ns = list(n) if isinstance(n, (list, tuple)) else [n] * len(index)
+        if len(ns) != len(index):
+            raise ValueError("restore: n holds one size per cloud (%d)" % len(index))
+        return [restore(v, i, m, fill) for v, i, m in zip(values, index, ns)]
+    if not torch.is_tensor(values) or not torch.is_tensor(index):
+        raise TypeError("restore: values and index must be tensors or lists of tensors")
+    if index.dtype not in (torch.int64, torch.int32):
+        raise TypeError("restore: index must be an integer tensor, got %s" % index.dtype)
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError("restore: n must be an integer >= 0, got %r" % (n,))
+    if index.dim() != 1 or values.dim() < 1 or values.shape[0] != index.shape[0]:
+        raise ValueError("restore: index (kept,) with values (kept,...); got %s and %s"
+                         % (tuple(index.shape), tuple(values.shape)))
+    if index.numel() and (int(index.min()) < 0 or int(index.max()) >= n):
+        raise ValueError("restore: index holds a row outside the %d points" % n)
+    out = torch.full((int(n),) + tuple(values.shape[1:]), fill, dtype=values.dtype, device=values.device)
+    out[index.long()] = values
+    return out

@@ -62,12 +62,17 @@ __global__ __launch_bounds__(256) void pn_knn3_kernel(const float* __restrict__ 
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int j = e * 64 + lane;
-    T d = (T)__builtin_inff();
+    // A slot past the segment takes the image 0, below (or equal to) the image of every value a point can have — of
+    // -inf and of a NaN too, which a non-finite coordinate produces.  With the image of -inf there, the query of a
+    // non-finite point (every distance a NaN, whose image lies below that of -inf) selected empty slots instead of
+    // points, and the sort below read keys that nobody had written.  Where every distance is finite nothing changes:
+    // every point outranked the empty slots before as well.
+    v[e] = 0;
     if (j < n) {
       const T dx = qx - (T)p[3 * j], dy = qy - (T)p[3 * j + 1], dz = qz - (T)p[3 * j + 2];
-      d = (dx * dx + dy * dy) + dz * dz;      // (-ffp-contract=off: three products and two sums, each rounded once)
+      const T d = (dx * dx + dy * dy) + dz * dz;      // (-ffp-contract=off: three products and two sums, each rounded once)
+      v[e] = Knn3Ord<T>::ord(-d);
     }
-    v[e] = Knn3Ord<T>::ord(-d);
   }
   const int kk = k < n ? k : n;
   // largest t with count(ord(v) >= t) >= kk: bit by bit from the top

@@ -365,6 +365,68 @@ def fps_ragged(pts, off, max_n, m, start=None, want_owner=False, want_radius=Fal
     return out if len(out) > 1 else sample
 
 
+OUTLIER_MIN_K, OUTLIER_MAX_K = 1, 64
+
+
+def outlier_stat(dist, off, k, std_ratio, want_index=True):
+    """Statistical outlier removal over a ragged batch (csrc/outlier.hip, definition csrc/outlier_math.h), exact and
+    bit-reproducible.  dist (total,k) fp32: the distances ``knn3_ragged`` (fp32) or ``knn3_grid`` returned with
+    ``want_dist``; off (S+1) int32 device offsets or the ``ragged.Clouds`` the points were flattened by; 1 <= k <= 64;
+    std_ratio finite and >= 0.
+    Returns (avg (total) fp64: the mean distance of every point to its min(k, n) nearest, itself included; stats (S,3)
+    fp64: mean, std and thr = mean + std_ratio * std of the valid (avg > 0) points of every segment; keep (total) bool:
+    avg > 0 and avg < thr; kept (S) int32: the kept points per segment) and, with ``want_index``, index (total) int32
+    last: the LOCAL indices of a segment's kept points, ascending, in the first kept[s] entries of its rows, -1 behind.
+    A segment that holds a non-finite coordinate (NaN rows of dist): NaN, nothing kept.  An empty segment: mean and thr
+    NaN, std 0.  ``pn_outlier_launches()`` = 6 stream-ordered launches on a workspace allocated here, no host
+    synchronisation."""
+    clouds = isinstance(off, Clouds)
+    require_cuda(dist, None if clouds else off)
+    dist = _f32c(dist, "dist")
+    k = int(k)
+    if not OUTLIER_MIN_K <= k <= OUTLIER_MAX_K:
+        raise ValueError("outlier_stat: k must be %d .. %d, got %d" % (OUTLIER_MIN_K, OUTLIER_MAX_K, k))
+    std_ratio = float(std_ratio)
+    if not 0.0 <= std_ratio < float("inf"):
+        raise ValueError("outlier_stat: std_ratio must be finite and not negative, got %r" % std_ratio)
+    if dist.dim() != 2 or dist.shape[1] != k:
+        raise ValueError("outlier_stat expects (total,%d) distances, got %s" % (k, tuple(dist.shape)))
+    total = dist.shape[0]
+    if total * k >= 2 ** 31:
+        raise ValueError("outlier_stat: total * k = %d (below 2^31)" % (total * k))
+    if clouds:
+        if total != off.total or dist.device != off.flat.device:
+            raise ValueError("outlier_stat: dist %s on %s does not belong to the Clouds given as off (%d points on %s)"
+                             % (tuple(dist.shape), dist.device, off.total, off.flat.device))
+        upload, S = off.device_offsets, off.S
+    else:
+        if off.dtype != torch.int32:
+            raise TypeError("off must be int32")
+        upload, S = off.contiguous, off.numel() - 1
+    dev = dist.device
+    S = max(S, 0)
+    avg = torch.empty(total, dtype=torch.float64, device=dev)
+    keep = torch.empty(total, dtype=torch.uint8, device=dev)
+    index = torch.empty(total, dtype=torch.int32, device=dev) if want_index else None
+    if total == 0:                                   # nothing to launch: every segment is empty
+        stats = torch.full((S, 3), float("nan"), dtype=torch.float64, device=dev)
+        stats[:, 1] = 0.0
+        kept = torch.zeros(S, dtype=torch.int32, device=dev)
+    else:
+        stats = torch.empty((S, 3), dtype=torch.float64, device=dev)
+        kept = torch.empty(S, dtype=torch.int32, device=dev)
+    if total > 0 and S > 0:
+        lib = _lib.load()
+        wsz = lib.pn_outlier_workspace_bytes(total, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_outlier_stat_f32(ptr(dist), ptr(upload()), S, total, k, std_ratio, ptr(avg), ptr(stats),
+                                         ptr(keep), ptr(kept), ptr(index), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_outlier_stat_f32")
+    out = (avg, stats, keep.view(torch.bool), kept)
+    return out + (index,) if want_index else out
+
+
 def _i64c(t, name):
     if t.dtype != torch.int64:
         raise TypeError("%s must be int64, got %s" % (name, t.dtype))

@@ -14,7 +14,7 @@ The definition (csrc/fps_math.h) is exact and bit-reproducible: squared distance
 distances.  csrc/fps.hip runs it from global memory over many workgroups, so no cloud size is a limit.
 
 Limits.  The sampling is sequential in m: m + 2 stream-ordered launches.  It picks outliers first: a scan with stray
-points should go through an outlier statistic before it.  ``owner`` is the nearest SAMPLE, not a surface projection:
+points goes through ``cleaning.remove_outliers`` before it.  ``owner`` is the nearest SAMPLE, not a surface projection:
 lifting labels across a thin wall follows Euclidean distance."""
 import numbers
 
