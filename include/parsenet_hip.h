@@ -949,6 +949,40 @@ int pn_outlier_stat_f32(const float* dist, const int* off, int S, int total, int
                         double* stats, uint8_t* keep, int32_t* kept, int32_t* index, void* ws, long long ws_bytes,
                         void* stream);
 
+/* ---- voxel-grid downsampling of clouds of any size, with the voxel of every point (csrc/voxel.hip, definition:
+ * csrc/voxel_math.h) ---------------------------------------------------------------------------------------------------
+ * pts (total,3) fp32, off (S+1) DEVICE int32 row offsets from 0 to total, voxel (S) fp32 DEVICE: the edge h of the
+ * cubic cells of every segment, origin (S,3) fp32 DEVICE or NULL (the per-axis minimum lo of the segment).  Per segment
+ * of n points: the cell of a point is c_a = floor(((double) x_a - (double) o_a) / (double) h) in fp64, a point on a
+ * face in the upper cell; a voxel is the set of points with the same cell triple, and voxels are numbered 0 .. V-1 by
+ * the ascending lowest point index they hold.  owner (total) int32: the number of every point's voxel (owner of a
+ * segment's first point is 0); nvox (S) int32: V.  centroid (total,3) fp32, count, first, rep (total) int32, any of them
+ * NULL: the voxel arrays of a segment occupy the first nvox[s] entries of the segment's own rows, NaN (centroid) and -1
+ * stand behind them — nothing is sized by a number that only the device knows.  centroid: with lo, hi the bounds of
+ * the segment, 2^E > max extent (frexp of the fp64 difference), s = 32 - E (0 for a zero extent) and
+ * u = llrint(((double) x - (double) lo) 2^s), (float) ((double) lo + ((double) SUM u / (double) count) 2^-s), the sum
+ * in 64-bit integers: exact in any order, within extent 2^-33 plus one fp32 rounding of the true mean.  first: the
+ * lowest LOCAL index of the voxel, ascending over the rows.  rep: the LOCAL index of the member with the smallest
+ * d = ((dx^2 + dy^2) + dz^2) to the fp32 centroid, every operation rounded once in fp32, no fma, the lowest index on
+ * equal d.  Status instead of V in nvox, with owner -1 throughout and no voxel rows (NaN / -1 in all of them): -1 for a
+ * segment that holds a non-finite coordinate; -2 ("voxel too small for the extent") where some c_a lies outside
+ * [-2^20, 2^20), where voxel[s] is not a positive finite number or an origin is not finite.  Rows that no valid segment
+ * of off holds are not written; a segment that does not lie inside 0 .. total gets nvox 0.  All outputs are functions
+ * of the segment's points, voxel[s] and origin[s] alone: the same bits from run to run and for every batching.
+ * pn_voxel_launches() = 7 stream-ordered kernel launches (two memsets come on top; 6 when rep is NULL), each over all
+ * segments; it needs no GPU.  No host synchronisation, no cooperative launch, no waiting between workgroups; the points
+ * of a voxel meet in 64-bit integer atomics (compare-and-swap on the cell key, add, min) on an open-addressing table of
+ * two slots per point.  Workspace of pn_voxel_workspace_bytes(total, S) bytes: 104 total + 12 (total / 1024 + S) +
+ * 40 S + 16, known from its arguments alone; 0 for total < 0, total >= 2^31 or S < 0.
+ * PN_ERR_ARG (before any launch) for S < 0, total < 0 (a total of 2^31 or more does not fit the int), a NULL pts, off,
+ * voxel, owner, nvox or ws, or a workspace that is too small; S == 0 or total == 0 returns 0 without a launch and
+ * writes nothing. */
+long long pn_voxel_workspace_bytes(long long total, int S);
+int pn_voxel_launches(void);
+int pn_voxel_f32(const float* pts, const int* off, int S, int total, const float* voxel, const float* origin,
+                 int32_t* owner, int32_t* nvox, float* centroid, int32_t* count, int32_t* first, int32_t* rep,
+                 void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

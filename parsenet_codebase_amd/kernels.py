@@ -365,6 +365,58 @@ def fps_ragged(pts, off, max_n, m, start=None, want_owner=False, want_radius=Fal
     return out if len(out) > 1 else sample
 
 
+VOXEL_OUTPUTS = ("centroid", "count", "first", "rep")
+
+
+def voxel_ragged(pts, off, voxel, origin=None, want=VOXEL_OUTPUTS):
+    """Voxel-grid downsampling of every segment of a ragged batch (csrc/voxel.hip, definition csrc/voxel_math.h), exact
+    and bit-reproducible.  pts (total,3) fp32, off (S+1) int32 device offsets or a ``ragged.Clouds``, voxel (S,) fp32 on
+    the device: the edge of the cubic cells of every segment, origin None (the per-axis minimum of the segment) or (S,3)
+    fp32 on the device; ``want``: which of "centroid", "count", "first", "rep" to compute.
+    Returns (owner (total,) int32: the number of every point's voxel — voxels are numbered by the ascending lowest
+    point index they hold —, nvox (S,) int32: the voxels of every segment) and then, in the order of ``VOXEL_OUTPUTS``,
+    the arrays named in ``want``: centroid (total,3) fp32, the exact mean of the voxel's points; count, first, rep
+    (total,) int32: its points, its lowest point index, and the point nearest to the centroid (LOCAL indices).  The
+    voxel arrays of a segment stand in the first nvox[s] entries of the segment's own rows, NaN / -1 behind them.
+    nvox -1: the segment holds a non-finite coordinate; -2: the voxel is too small for the extent (a cell index outside
+    -2^20 .. 2^20 - 1) or no positive finite number; both: owner -1, no voxel rows.
+    ``pn_voxel_launches()`` = 7 stream-ordered launches on a workspace allocated here, no host synchronisation."""
+    require_cuda(voxel, origin)
+    pts, upload, S, _ = _device_offsets("voxel_ragged", pts, off, 0)
+    unknown = [w for w in want if w not in VOXEL_OUTPUTS]
+    if unknown:
+        raise ValueError("voxel_ragged: want holds %s, got %r" % (", ".join(VOXEL_OUTPUTS), unknown))
+    total, S, dev = pts.shape[0], max(S, 0), pts.device
+    if total >= 2 ** 31:
+        raise ValueError("voxel_ragged: total = %d (below 2^31)" % total)
+    voxel = _f32c(voxel, "voxel")
+    if tuple(voxel.shape) != (S,) or voxel.device != dev:
+        raise ValueError("voxel_ragged: voxel must be (%d,) on %s, got %s on %s" % (S, dev, tuple(voxel.shape),
+                                                                                      voxel.device))
+    if origin is not None:
+        origin = _f32c(origin, "origin")
+        if tuple(origin.shape) != (S, 3) or origin.device != dev:
+            raise ValueError("voxel_ragged: origin must be (%d,3) on %s, got %s on %s" % (S, dev, tuple(origin.shape),
+                                                                                           origin.device))
+    owner = torch.empty(total, dtype=torch.int32, device=dev)
+    out = {"centroid": torch.empty((total, 3), dtype=torch.float32, device=dev) if "centroid" in want else None}
+    for name in VOXEL_OUTPUTS[1:]:
+        out[name] = torch.empty(total, dtype=torch.int32, device=dev) if name in want else None
+    if total == 0:                                    # nothing to launch: every segment is empty
+        nvox = torch.where((voxel > 0) & torch.isfinite(voxel), 0, -2).to(torch.int32)
+    else:
+        nvox = torch.empty(S, dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        wsz = lib.pn_voxel_workspace_bytes(total, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_voxel_f32(ptr(pts), ptr(upload()), S, total, ptr(voxel), ptr(origin), ptr(owner), ptr(nvox),
+                                  ptr(out["centroid"]), ptr(out["count"]), ptr(out["first"]), ptr(out["rep"]), ptr(ws),
+                                  wsz, current_stream(dev))
+        check(rc, "pn_voxel_f32")
+    return (owner, nvox) + tuple(out[name] for name in VOXEL_OUTPUTS if name in want)
+
+
 OUTLIER_MIN_K, OUTLIER_MAX_K = 1, 64
 
 

@@ -15,7 +15,15 @@ distances.  csrc/fps.hip runs it from global memory over many workgroups, so no 
 
 Limits.  The sampling is sequential in m: m + 2 stream-ordered launches.  It picks outliers first: a scan with stray
 points goes through ``cleaning.remove_outliers`` before it.  ``owner`` is the nearest SAMPLE, not a surface projection:
-lifting labels across a thin wall follows Euclidean distance."""
+lifting labels across a thin wall follows Euclidean distance.
+
+A dense, unevenly sampled scan goes through ``voxel_downsample`` first: one point per occupied cell of a cubic grid
+(csrc/voxel_math.h, csrc/voxel.hip: exact centroids from 64-bit integer sums, seven launches whatever the size), which
+equalises the density and leaves the sequential sampling a tenth of the points.  The two owners compose:
+
+    vox, nrm_v, own_v = voxel_downsample(pts, h, nrm, position="point")
+    red, nrm_r, own_f = reduce_cloud(vox, 10000, nrm_v)
+    labels = lift(lift(labels_r, own_f), own_v)"""
 import numbers
 
 import numpy as np
@@ -95,6 +103,112 @@ def reduce_cloud(points, m, *per_point, start=None):
     for a in (clouds.flat,) + tuple(clouds.beside(a, who, "a per-point array") for a in per_point):
         res.append(clouds.per_cloud(a[rows].reshape((clouds.S, int(m)) + tuple(a.shape[1:]))))
     return tuple(res) + (clouds.per_point(out[1].long()),)
+
+
+def _positive(v):
+    """Is v a number (no bool) that is positive and finite as fp32?"""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        return False
+    try:
+        with np.errstate(over="ignore"):
+            f = np.float32(v)
+    except OverflowError:
+        return False
+    return bool(f > 0 and np.isfinite(f))
+
+
+def _voxel_sizes(voxel, S, who):
+    """A positive finite number or one per cloud -> (S,) fp32 on the host."""
+    if isinstance(voxel, (list, tuple, np.ndarray)) or torch.is_tensor(voxel):
+        sizes = voxel.tolist() if isinstance(voxel, np.ndarray) or torch.is_tensor(voxel) else list(voxel)
+        if not isinstance(sizes, list):
+            sizes = [sizes] * S                                                   # (a 0-d array or tensor)
+        elif len(sizes) != S:
+            raise ValueError("%s: voxel holds one size per cloud (%d), got %d" % (who, S, len(sizes)))
+    else:
+        sizes = [voxel] * S
+    if not all(_positive(v) for v in sizes):
+        raise ValueError("%s: voxel must be a positive finite number or one per cloud, got %r" % (who, voxel))
+    return np.asarray(sizes, dtype=np.float32)
+
+
+def _voxel_origins(origin, S, who):
+    """None, 3 numbers or 3 per cloud -> None or (S,3) fp32 on the host."""
+    if origin is None:
+        return None
+    try:
+        if torch.is_tensor(origin):
+            origin = origin.detach().cpu().numpy()
+        if isinstance(origin, (str, bytes)) or any(isinstance(v, bool) for v in np.asarray(origin, object).ravel()):
+            raise TypeError
+        with np.errstate(over="ignore"):
+            o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        o = None
+    if o is not None and o.shape == (3,):
+        o = np.tile(o, (S, 1))
+    if o is None or o.shape != (S, 3) or not np.isfinite(o).all():
+        raise ValueError("%s: origin must be None, 3 finite numbers or 3 per cloud (%d), got %r" % (who, S, origin))
+    return np.ascontiguousarray(o)
+
+
+def voxel_downsample(points, voxel, *per_point, origin=None, position="centroid", return_info=False):
+    """The first step on a dense scan: one point per occupied cell of a cubic grid, and for every scanned point the
+    voxel that holds it.  (reduced, *[a[rep] for a in per_point], owner).
+
+    points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
+    voxel: the edge of the cells, a positive finite number, or one per cloud.
+    origin: a corner of the grid — None (the per-axis minimum of every cloud), 3 numbers, or 3 per cloud.  The cell of
+       a point is floor((x - origin) / voxel) per axis, in fp64; a point on a face belongs to the upper cell.
+    position: "centroid" — ``reduced`` holds the exact mean of every voxel's points, which averages sensor noise away
+       — or "point" — ``reduced`` is ``points[rep]``, rep the point of the voxel nearest to its centroid: actual scan
+       points, which lie on the surface.
+    per_point: arrays with one row per point (normals, colours, labels) of any dtype, in the layout of ``points``:
+       (N,...), (B,N,...) or lists of (N_b,...).  They are GATHERED at the representative, exact rows — right for
+       labels, and right for normals at a crease.  Averaged attributes per voxel are out of scope.
+    Voxels are numbered by the ascending lowest point index they hold.  ``owner``, int64 in the layout of the points,
+    (N,), (B,N) or a list, is the number of every point's voxel — keep it for ``lift``.  With ``return_info`` also
+    ``count`` and ``rep`` (int64, per voxel: its points, and the index of its representative in the cloud) last.
+    A single cloud comes back as tensors; a batch or a list comes back as LISTS of tensors, one per cloud, because the
+    voxel counts differ (as in ``cleaning.remove_outliers``).  A cloud that holds a non-finite coordinate gives zero
+    voxels and owner -1, which ``lift`` refuses.  Raises ValueError ("voxel too small", naming the cloud) where a cell
+    index leaves -2^20 .. 2^20 - 1.  All results are functions of the cloud, the voxel and the origin alone
+    (csrc/voxel_math.h).  Seven stream-ordered launches and exactly one host read: the voxel counts, which size the
+    results."""
+    who = "voxel_downsample"
+    if position not in ("centroid", "point"):
+        raise ValueError('%s: position must be "centroid" or "point", got %r' % (who, position))
+    if isinstance(points, (list, tuple)):
+        S = len(points)
+    else:
+        S = int(points.shape[0]) if torch.is_tensor(points) and points.dim() == 3 else 1
+    sizes, origins = _voxel_sizes(voxel, S, who), _voxel_origins(origin, S, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    beside = tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    dev = clouds.flat.device
+    want = (("centroid",) if position == "centroid" else ()) + (("count",) if return_info else ()) + ("rep",)
+    out = K.voxel_ragged(clouds.flat, clouds, _lib.h2d(sizes, dev), None if origins is None else _lib.h2d(origins, dev),
+                         want=want)
+    found = dict(zip(("owner", "nvox") + want, out))
+    from .cleaning import _read_counts
+    counts = _read_counts(found["nvox"])
+    for c, v in enumerate(counts):
+        if v == -2:
+            raise ValueError("%s: cloud %d: voxel too small for the extent of the cloud (a cell index outside "
+                             "-2^20 .. 2^20 - 1), voxel = %r" % (who, c, float(sizes[c])))
+    counts = [max(v, 0) for v in counts]
+    base = clouds.off[:-1].tolist()
+    head = [torch.arange(o, o + v, device=dev) for o, v in zip(base, counts)]       # the voxel rows of every cloud
+    first = [torch.full((v,), o, dtype=torch.int64, device=dev) for o, v in zip(base, counts)]
+    head, first = (part[0] if len(part) == 1 else torch.cat(part) for part in (head, first))
+    rep = found["rep"][head].long()                                                 # LOCAL to the cloud
+    rows = rep + first                                                              # ... and of the flat arrays
+    reduced = found["centroid"][head] if position == "centroid" else clouds.flat[rows]
+    res = [reduced] + [a[rows] for a in beside]
+    info = [found["count"][head].long(), rep] if return_info else []
+    single = clouds.layout == "single"
+    res, info = ([a if single else list(torch.split(a, counts)) for a in part] for part in (res, info))
+    return tuple(res) + (clouds.per_point(found["owner"].long()),) + tuple(info)
 
 
 def lift(values, owner):
