@@ -262,7 +262,8 @@ def fit_cone(points, normals, weights):
     A = weights * normals
     Y = weights * (normals * points).sum(1).reshape((N, 1))
     if np.linalg.cond(A.detach().numpy()) > 1e5:
-        return torch.zeros((1, 3)), torch.tensor([[1.0, 0.0, 0.0]]), torch.zeros(1)
+        dt = points.dtype
+        return torch.zeros((1, 3), dtype=dt), torch.tensor([[1.0, 0.0, 0.0]], dtype=dt), torch.zeros(1, dtype=dt)
     c = lstsq(A, Y, 1e-3)
     a, _ = fit_plane(normals, weights)
     if (normals @ a.t()).sum() > 0:

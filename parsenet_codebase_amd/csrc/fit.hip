@@ -15,10 +15,16 @@ __global__ void pn_sym3_eig_kernel(const double* __restrict__ G, int M, double* 
       a[i][j] = 0.5 * (G[(size_t)t * 9 + i * 3 + j] + G[(size_t)t * 9 + j * 3 + i]);
       v[i][j] = i == j ? 1.0 : 0.0;
     }
+  bool settled = false;
   for (int sweep = 0; sweep < 32; ++sweep) {
     const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
     const double diag = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
     if (off <= 1e-300 || off <= 1e-18 * diag) break;
+    // One sweep that starts at rounding level squares `off` and ends the loop above — unless two eigenvalues
+    // coincide: there the rotations are O(1) angles decided by rounding, `off` stays at rounding level and all
+    // 32 sweeps would wear out the orthogonality of V (150 ulp instead of 20).  So that sweep is the last one.
+    if (settled) break;
+    settled = off <= 8.0 * 2.220446049250313e-16 * diag;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
         if (a[p][q] == 0.0) continue;

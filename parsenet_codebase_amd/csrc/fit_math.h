@@ -110,10 +110,16 @@ FB_HD void jacobi3(const double G[3][3], double w[3], double V[3][3]) {
       a[i][j] = 0.5 * (G[i][j] + G[j][i]);
       v[i][j] = i == j ? 1.0 : 0.0;
     }
+  bool settled = false;
   for (int sweep = 0; sweep < 32; ++sweep) {
     const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
     const double diag = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
     if (off <= 1e-300 || off <= 1e-18 * diag) break;
+    // One sweep that starts at rounding level squares `off` and ends the loop above — unless two eigenvalues
+    // coincide: there the rotations are O(1) angles decided by rounding, `off` stays at rounding level and all
+    // 32 sweeps would wear out the orthogonality of V (150 ulp instead of 20).  So that sweep is the last one.
+    if (settled) break;
+    settled = off <= 8.0 * 2.220446049250313e-16 * diag;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
         if (a[p][q] == 0.0) continue;
@@ -232,6 +238,7 @@ FB_HD void solve3(const Dd A_[3][3], const Dd b_[3], Dd x[3]) {
 FB_HD int lstsq3(const Dd G_[3][3], const Dd rhs_[3], int n_rows, Dd x[3], double* lambda_used) {
   Dd M[3][3], r[3];
   for (int i = 0; i < 3; ++i) {
+    x[i] = mk(0.0);   // what a failed system (return 1) leaves behind
     r[i] = rhs_[i];
     for (int j = 0; j < 3; ++j) M[i][j] = G_[i][j];
   }
