@@ -983,6 +983,41 @@ int pn_voxel_f32(const float* pts, const int* off, int S, int total, const float
                  int32_t* owner, int32_t* nvox, float* centroid, int32_t* count, int32_t* first, int32_t* rep,
                  void* ws, long long ws_bytes, void* stream);
 
+/* ---- Euclidean cluster extraction on clouds of any size (csrc/cluster.hip, definition: csrc/cluster_math.h) ----------
+ * pts (total,3) fp32, off (S+1) DEVICE int32 row offsets from 0 to total, max_n >= the largest segment (a host integer:
+ * it alone fixes the schedule), radius (S) fp32 DEVICE: the radius r of every segment, min_size >= 1.  Per segment of n
+ * points, indices LOCAL to it, r2 = fl(r * r) in fp32: {i, j}, i != j, is an edge iff
+ * d = ((x_i-x_j)^2 + (y_i-y_j)^2) + (z_i-z_j)^2 <= r2, every operation rounded once in fp32, no fma (equality is an
+ * edge); a component is a connected component of that graph, kept iff it holds at least min_size points; the kept
+ * components are numbered 0 .. C-1 by their ascending lowest point index.  label (total) int32: the number of every
+ * point's component, -1 for a point of a dropped component; ncomp (S) int32: C.  count, first (total) int32 or NULL: the
+ * size and the lowest LOCAL index of the kept components in the first ncomp[s] entries of the segment's own rows
+ * (first ascends), -1 behind them — nothing is sized by a number that only the device knows.  ndrop (S) int32 or NULL:
+ * the points of the segment with label -1.  Status instead of C in ncomp, with label, count and first -1 throughout and
+ * ndrop n: -1 for a segment that holds a non-finite coordinate (flagged while the bounding box is taken, never
+ * searched); -2 where r or r2 is not a positive finite number (r = 1e-30: r2 underflows).  Rows that no valid segment
+ * of off holds are not written; a segment that does not lie inside 0 .. total gets ncomp 0 (and ndrop 0).  All outputs
+ * are functions of the segment's points, radius[s] and min_size alone: the same bits from run to run and for every
+ * batching.
+ * The neighbours come from an exact uniform-grid search (the cells and the bound of csrc/knn3_grid_math.h, a cell edge
+ * not below r where the cloud allows it); the components from ceil(log2 max_n) + 1 Boruvka rounds in global memory —
+ * one offer launch (every point searches its ball; one 64-bit integer atomic minimum per point), one hook launch and
+ * ceil(log_64 max_n) compress launches each — between four launches that build the grid and three that number the
+ * components: pn_cluster_launches(max_n) = 4 + (ceil(log2 max_n) + 1) (2 + ceil(log_64 max_n)) + 3 kernel launches
+ * (three memsets come on top); it needs no GPU.  All of it is stream-ordered: no host synchronisation, no cooperative
+ * launch, no waiting between workgroups; once no component finds an edge the remaining rounds exit at a device flag.
+ * A max_n below the largest segment can end the rounds early (components left apart, never an access outside the
+ * buffers).  Workspace of pn_cluster_workspace_bytes(total, S) bytes: 56 total + 36 S + 1296, known from its arguments
+ * alone; 0 for total < 0, total >= 2^31 or S < 0.  Its first 32 words (after alignment to 16 bytes) hold, after the
+ * call, 1 for every round in which a component found an edge.
+ * PN_ERR_ARG (before any launch) for S < 0, total < 0, max_n < 0, min_size < 1, a NULL pts, off, radius, label, ncomp
+ * or ws, or a workspace that is too small; S == 0 or total == 0 returns 0 without a launch and writes nothing. */
+long long pn_cluster_workspace_bytes(long long total, int S);
+int pn_cluster_launches(int max_n);
+int pn_cluster_f32(const float* pts, const int* off, int S, int total, int max_n, const float* radius, int min_size,
+                   int32_t* label, int32_t* ncomp, int32_t* count, int32_t* first, int32_t* ndrop, void* ws,
+                   long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,16 +19,35 @@ ragged batch, without atomics, on clouds of any size.
 Limits.  The statistic is global per cloud: a scan whose density varies strongly (a near and a far surface in one
 cloud) loses the sparse part first.  The distances are fp32, so a point whose statistic lies within about 1e-6 relative
 of the threshold may fall on the other side than with open3d's fp64 distances.  ``fitting_eval.outlier_keep_mask`` (the
-fixed (20, 0.5) filter of the evaluation-mode spline segments, on fp64 distances) is a different tool and stays."""
+fixed (20, 0.5) filter of the evaluation-mode spline segments, on fp64 distances) is a different tool and stays.
+The statistic removes ISOLATED strays: a clump of thirty stray points has small neighbour distances and survives it.
+
+A scan is rarely one shape: several parts on a table, a part and its fixture, a part and a clump of debris.
+``euclidean_clusters`` labels the connected components of the graph "no further apart than a radius" (Euclidean
+cluster extraction; csrc/cluster_math.h, exact, csrc/cluster.hip), ``split_clusters`` hands every object out on its own
+and ``keep_largest`` keeps the object and drops the debris.  Every object then goes through the pipeline alone, at the
+density the network was trained at:
+
+    split_clusters → per object: remove_outliers → voxel_downsample → reduce_cloud → network → lift → lift → restore → restore
+
+    for pts_c, nrm_c, index_c in split_clusters(scan, normals, radius=3 * spacing, min_size=50):
+        ...                                                              # the pipeline above on pts_c
+        labels = restore(labels_c, index_c, n, -1)                       # back to the n scanned points
+
+Limits of the clusters.  A radius far above the point spacing costs the points in the ball per point and round.  Two
+objects that touch (closer than the radius anywhere) are one component.  A label -1 means "dropped" (a component below
+min_size), not "outlier"."""
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib
 from . import kernels as K
 from .point_normals import _search
 from .ragged import Clouds
+from .sampling import _positive_per_cloud
 
 
 def _arguments(k, std_ratio, who):
@@ -111,6 +130,122 @@ def _read_counts(kept):
         return [int(c) for c in host.tolist()]
     finally:
         _lib._PinnedRing.release(slot)
+
+
+def _cluster_arguments(points, radius, min_size, who):
+    """The checks of the three cluster functions, before anything touches the GPU -> ((S,) fp32 radii on the host,
+    min_size)."""
+    if isinstance(points, (list, tuple)):
+        S = len(points)
+    else:
+        S = int(points.shape[0]) if torch.is_tensor(points) and points.dim() == 3 else 1
+    radii = _positive_per_cloud(radius, S, who, "radius", "number")
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or not 1 <= min_size < 2 ** 31:
+        raise ValueError("%s: min_size must be an integer >= 1, got %r" % (who, min_size))
+    return radii, int(min_size)
+
+
+def euclidean_clusters(points, radius, min_size=1, return_info=False):
+    """Which object of the scan every point belongs to: Euclidean cluster extraction (PCL's EuclideanClusterExtraction,
+    open3d's cluster_dbscan with min_points = 1).
+
+    points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
+    radius: a positive finite number, or one per cloud (host numbers: a list, an array, a CPU tensor; a GPU tensor is
+       read on the host first, which is a synchronisation).  Two points belong together when a chain of points links
+       them and no step of the chain is longer than the radius (fp32 squared distances against fl(radius^2); equality
+       links).  A few times the point spacing is the usual choice.
+    min_size: an integer >= 1; a component of fewer points is dropped.
+    Returns ``label``, int32 in the layout of the points, (N,), (B,N) or a list of (N_b,): the number of every point's
+    component — the kept components of a cloud are numbered 0 .. C-1 by the ascending lowest point index they hold —
+    and -1 for a point of a dropped component.  With ``return_info`` a tuple (label, ncomp, count, first): ncomp int32,
+    a scalar, (B,) or a list of scalars, the kept components C of every cloud; count and first, int32 in the layout of
+    the points: the size and the lowest point index of component c in row c < C, -1 behind.  ncomp -1: the cloud holds a
+    non-finite coordinate; -2: the square of its radius under- or overflows in fp32; both with label -1 throughout.
+    All results are functions of the cloud, its radius and min_size alone (csrc/cluster_math.h), the same bits from
+    run to run and for every batching.  One ``kernels.cluster_ragged`` call, no host synchronisation (with the radius
+    given as host numbers)."""
+    who = "euclidean_clusters"
+    radii, min_size = _cluster_arguments(points, radius, min_size, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    want = ("count", "first") if return_info else ()
+    out = K.cluster_ragged(clouds.flat, clouds, _lib.h2d(radii, clouds.flat.device), min_size, want=want)
+    label = clouds.per_point(out[0])
+    if not return_info:
+        return label
+    return label, clouds.per_cloud(out[1]), clouds.per_point(out[2]), clouds.per_point(out[3])
+
+
+def _components(clouds, radii, min_size, who):
+    """One ``K.cluster_ragged`` call and the one host read (ncomp and the component sizes, one download) -> per cloud
+    the sizes of its kept components (a list of lists) and their flat rows (a list of lists of int64 tensors, the rows
+    of every component ascending).  Raises ValueError for a cloud with status -2; one with -1 has no component."""
+    dev = clouds.flat.device
+    label, ncomp, count = K.cluster_ragged(clouds.flat, clouds, _lib.h2d(radii, dev), min_size, want=("count",))
+    host = _read_counts(torch.cat([ncomp, count]))
+    S, base = clouds.S, clouds.off[:-1].tolist()
+    for c, v in enumerate(host[:S]):
+        if v == -2:
+            raise ValueError("%s: cloud %d: the square of radius = %r is no positive finite fp32 number"
+                             % (who, c, float(radii[c])))
+    found = [max(v, 0) for v in host[:S]]
+    sizes = [host[S + o:S + o + v] for o, v in zip(base, found)]
+    flat_sizes = [m for part in sizes for m in part]
+    if not flat_sizes:
+        return sizes, [[] for _ in range(S)]
+    # a stable sort by (cloud, component) keeps the rows of every component ascending; dropped points go last
+    before = np.cumsum([0] + found[:-1])
+    shift = torch.repeat_interleave(_lib.h2d(before.astype(np.int64), dev),
+                                    _lib.h2d(np.asarray(clouds.sizes, dtype=np.int64), dev), output_size=clouds.total)
+    key = torch.where(label >= 0, label.long() + shift, len(flat_sizes))
+    rows = torch.sort(key, stable=True).indices[:sum(flat_sizes)]
+    pieces = iter(torch.split(rows, flat_sizes))
+    return sizes, [[next(pieces) for _ in part] for part in sizes]
+
+
+def split_clusters(points, *per_point, radius, min_size=1, order="index"):
+    """Take a scan apart into its objects, in front of everything else: for every kept component
+    (points[index], *[a[index] for a in per_point], index).
+
+    points, radius, min_size: as in ``euclidean_clusters``.  per_point: arrays with one row per point (normals, colours,
+    labels) in the layout of ``points``.  order: "index" — the components in the order of their lowest point, as they
+    are numbered — or "size" — the largest first, ties by the lowest point.
+    One cloud gives a list over its components; a batch or a list of clouds gives a list of such lists.  ``index``,
+    int64, holds the original rows of the component, ascending — keep it for ``restore``.  Points of components below
+    min_size are in no component.  A cloud that holds a non-finite coordinate gives no component; a radius whose square
+    under- or overflows in fp32 raises ValueError, naming the cloud.
+    Exactly one host read: the number of components and their sizes, which size the results."""
+    who = "split_clusters"
+    if order not in ("index", "size"):
+        raise ValueError('%s: order must be "index" or "size", got %r' % (who, order))
+    radii, min_size = _cluster_arguments(points, radius, min_size, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    beside = tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    sizes, rows = _components(clouds, radii, min_size, who)
+    out = []
+    for o, part, m in zip(clouds.off[:-1].tolist(), rows, sizes):
+        ranks = range(len(part)) if order == "index" else sorted(range(len(part)), key=lambda c: (-m[c], c))
+        out.append([tuple(a[part[c]] for a in (clouds.flat,) + beside) + (part[c] - o,) for c in ranks])
+    return out[0] if clouds.layout == "single" else out
+
+
+def keep_largest(points, *per_point, radius):
+    """The object of the scan, without the debris around it: (points[index], *[a[index] for a in per_point], index) of
+    the largest connected component of every cloud, ties by the lowest point — the shape of ``remove_outliers``, whose
+    statistic a clump of stray points survives.  points, radius, per_point: as in ``split_clusters``.  A single cloud
+    comes back as tensors, a batch or a list as LISTS of tensors, one per cloud; ``index``, int64, ascending, is ready
+    for ``restore``.  An empty cloud, or one that holds a non-finite coordinate, comes back empty; a radius whose
+    square under- or overflows in fp32 (1e-30) raises ValueError, naming the cloud, as in ``split_clusters``.  Exactly
+    one host read."""
+    who = "keep_largest"
+    radii, _ = _cluster_arguments(points, radius, 1, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    beside = tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    sizes, rows = _components(clouds, radii, 1, who)
+    none = torch.empty(0, dtype=torch.int64, device=clouds.flat.device)
+    picked = [part[max(range(len(part)), key=lambda c: (m[c], -c))] if part else none for part, m in zip(rows, sizes)]
+    res = [[a[p] for p in picked] for a in (clouds.flat,) + beside]
+    res.append([p - o for p, o in zip(picked, clouds.off[:-1].tolist())])
+    return tuple(part[0] if clouds.layout == "single" else part for part in res)
 
 
 def restore(values, index, n, fill):

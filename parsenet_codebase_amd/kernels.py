@@ -1,6 +1,8 @@
 """Tensor-level wrappers over the C ABI.  Each function validates layout, allocates
 outputs/workspace through torch's caching allocator and launches on torch's current
 HIP stream.  No arithmetic happens here."""
+import numbers
+
 import numpy as np
 import torch
 
@@ -415,6 +417,62 @@ def voxel_ragged(pts, off, voxel, origin=None, want=VOXEL_OUTPUTS):
                                   wsz, current_stream(dev))
         check(rc, "pn_voxel_f32")
     return (owner, nvox) + tuple(out[name] for name in VOXEL_OUTPUTS if name in want)
+
+
+CLUSTER_OUTPUTS = ("count", "first", "ndrop")
+
+
+def cluster_ragged(pts, off, radius, min_size=1, want=CLUSTER_OUTPUTS):
+    """Euclidean cluster extraction of every segment of a ragged batch (csrc/cluster.hip, definition
+    csrc/cluster_math.h), exact and bit-reproducible.  pts (total,3) fp32, off (S+1) int32 device offsets or a
+    ``ragged.Clouds``, radius (S,) fp32 on the device: two points of a segment are joined when their fp32 squared
+    distance is at most fl(r * r); min_size >= 1: a connected component of fewer points is dropped; ``want``: which of
+    "count", "first", "ndrop" to compute.
+    Returns (label (total,) int32: the number of every point's component — kept components are numbered by the ascending
+    lowest point index they hold —, -1 for a point of a dropped component; ncomp (S,) int32: the kept components of
+    every segment) and then, in the order of ``CLUSTER_OUTPUTS``, the arrays named in ``want``: count, first (total,)
+    int32, the size and the lowest LOCAL index of the kept components in the first ncomp[s] entries of the segment's own
+    rows, -1 behind them; ndrop (S,) int32, the points with label -1.  ncomp -1: the segment holds a non-finite
+    coordinate; -2: the radius or its square is no positive finite number; both: label, count, first -1 throughout.
+    The schedule is fixed by the largest segment of a Clouds, by total under plain offsets:
+    ``pn_cluster_launches(max_n)`` stream-ordered launches on a workspace allocated here, no host synchronisation."""
+    if not torch.is_tensor(radius):
+        raise TypeError("cluster_ragged: radius must be a tensor, got %s" % type(radius).__name__)
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or not 1 <= min_size < 2 ** 31:
+        raise ValueError("cluster_ragged: min_size must be an integer >= 1, got %r" % (min_size,))
+    unknown = [w for w in want if w not in CLUSTER_OUTPUTS]
+    if unknown:
+        raise ValueError("cluster_ragged: want holds %s, got %r" % (", ".join(CLUSTER_OUTPUTS), unknown))
+    require_cuda(radius)
+    pts, upload, S, max_n = _device_offsets("cluster_ragged", pts, off, None if isinstance(off, Clouds) else 0)
+    total, S, dev = pts.shape[0], max(S, 0), pts.device
+    if total >= 2 ** 31:
+        raise ValueError("cluster_ragged: total = %d (below 2^31)" % total)
+    if not isinstance(off, Clouds):
+        max_n = total
+    radius = _f32c(radius, "radius")
+    if tuple(radius.shape) != (S,) or radius.device != dev:
+        raise ValueError("cluster_ragged: radius must be (%d,) on %s, got %s on %s" % (S, dev, tuple(radius.shape),
+                                                                                        radius.device))
+    label = torch.empty(total, dtype=torch.int32, device=dev)
+    out = {name: torch.empty(total, dtype=torch.int32, device=dev) if name in want else None
+           for name in CLUSTER_OUTPUTS[:2]}
+    if total == 0:                                    # nothing to launch: every segment is empty
+        r2 = radius * radius
+        ncomp = torch.where((radius > 0) & torch.isfinite(radius) & (r2 > 0) & torch.isfinite(r2), 0, -2).to(torch.int32)
+        out["ndrop"] = torch.zeros(S, dtype=torch.int32, device=dev) if "ndrop" in want else None
+    else:
+        ncomp = torch.empty(S, dtype=torch.int32, device=dev)
+        out["ndrop"] = torch.empty(S, dtype=torch.int32, device=dev) if "ndrop" in want else None
+        lib = _lib.load()
+        wsz = lib.pn_cluster_workspace_bytes(total, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_cluster_f32(ptr(pts), ptr(upload()), S, total, int(max_n), ptr(radius), int(min_size),
+                                    ptr(label), ptr(ncomp), ptr(out["count"]), ptr(out["first"]), ptr(out["ndrop"]),
+                                    ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_cluster_f32")
+    return (label, ncomp) + tuple(out[name] for name in CLUSTER_OUTPUTS if name in want)
 
 
 OUTLIER_MIN_K, OUTLIER_MAX_K = 1, 64

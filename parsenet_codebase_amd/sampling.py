@@ -117,19 +117,25 @@ def _positive(v):
     return bool(f > 0 and np.isfinite(f))
 
 
+def _positive_per_cloud(value, S, who, name, noun):
+    """A positive finite number or one per cloud -> (S,) fp32 on the host; ``name`` and ``noun`` word the errors
+    ("voxel holds one size per cloud").  A tensor is read on the host (a GPU tensor: one synchronisation)."""
+    if isinstance(value, (list, tuple, np.ndarray)) or torch.is_tensor(value):
+        each = value.tolist() if isinstance(value, np.ndarray) or torch.is_tensor(value) else list(value)
+        if not isinstance(each, list):
+            each = [each] * S                                                     # (a 0-d array or tensor)
+        elif len(each) != S:
+            raise ValueError("%s: %s holds one %s per cloud (%d), got %d" % (who, name, noun, S, len(each)))
+    else:
+        each = [value] * S
+    if not all(_positive(v) for v in each):
+        raise ValueError("%s: %s must be a positive finite number or one per cloud, got %r" % (who, name, value))
+    return np.asarray(each, dtype=np.float32)
+
+
 def _voxel_sizes(voxel, S, who):
     """A positive finite number or one per cloud -> (S,) fp32 on the host."""
-    if isinstance(voxel, (list, tuple, np.ndarray)) or torch.is_tensor(voxel):
-        sizes = voxel.tolist() if isinstance(voxel, np.ndarray) or torch.is_tensor(voxel) else list(voxel)
-        if not isinstance(sizes, list):
-            sizes = [sizes] * S                                                   # (a 0-d array or tensor)
-        elif len(sizes) != S:
-            raise ValueError("%s: voxel holds one size per cloud (%d), got %d" % (who, S, len(sizes)))
-    else:
-        sizes = [voxel] * S
-    if not all(_positive(v) for v in sizes):
-        raise ValueError("%s: voxel must be a positive finite number or one per cloud, got %r" % (who, voxel))
-    return np.asarray(sizes, dtype=np.float32)
+    return _positive_per_cloud(voxel, S, who, "voxel", "size")
 
 
 def _voxel_origins(origin, S, who):
