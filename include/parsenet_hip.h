@@ -1018,6 +1018,37 @@ int pn_cluster_f32(const float* pts, const int* off, int S, int total, int max_n
                    int32_t* label, int32_t* ncomp, int32_t* count, int32_t* first, int32_t* ndrop, void* ws,
                    long long ws_bytes, void* stream);
 
+/* ---- Dominant-plane extraction on clouds of any size (csrc/plane.hip, definition: csrc/plane_math.h) -----------------
+ * pts (total,3) fp32, off (S+1) DEVICE int32 row offsets from 0 to total, threshold (S) fp32 DEVICE: the threshold t of
+ * every segment, H hypotheses (1 .. 4096), seed: 64 bits, passed as the bits of a long long, refine: 0 .. 4 rounds, axis:
+ * NULL or three HOST doubles of unit length with min_cos in [0, 1].  Per segment of n points, indices LOCAL to it:
+ * hypothesis h is the plane (n, d), |n| = 1 in fp64 with the component of largest magnitude positive, through the
+ * points ((splitmix64(seed + 0x9E3779B97F4A7C15 (3 h + s + 1)) >> 32) n) >> 32, s = 0, 1, 2; it is invalid when two of
+ * them are equal, when they are collinear and, with an axis, when |n . axis| < min_cos.  A point is an inlier iff
+ * |((nx x + ny y) + nz z) + d| <= (double) t in fp64, every operation rounded once.  The valid hypothesis with the most
+ * inliers wins, the lowest h on equal counts; every refinement round replaces the plane by the least-squares plane
+ * through its inliers (fp64 moments summed by the fixed tree of csrc/outlier_math.h, the Jacobi solver of
+ * csrc/normal_math.h) iff that plane is not degenerate, satisfies the axis constraint and has at least as many inliers.
+ *   plane (S,4) fp64: nx, ny, nz, d; count (S) int32: its inliers; best (S) int32: the winning h, whatever the refinement
+ *   did, -1 without a valid hypothesis (count 0, plane zeros); inlier (total) one byte per point; dist (total) fp32 or
+ *   NULL: the signed distance of every point, formed in fp64 and rounded once, NaN in a segment without a plane.
+ *   count -1: the segment holds a non-finite coordinate; -2: t is no positive finite number; both: best -1, plane zeros,
+ *   no inlier.  A point that no valid segment of off holds gets inlier 0 and dist NaN.
+ * All outputs are functions of the segment and the arguments alone: the same bits from run to run and for every
+ * batching.  pn_plane_launches(refine) = 5 + 6 refine stream-ordered kernel launches (0 for refine outside 0 .. 4); it
+ * needs no GPU.  No host synchronisation, no cooperative launch, no waiting between workgroups; the inlier counts of a
+ * hypothesis meet in integer atomic additions.  Workspace of pn_plane_workspace_bytes(total, S, H) bytes:
+ * 36 S H + 64 (total / 1024 + S) + 60 S + 16, known from its arguments alone; 0 for total < 0, total >= 2^31, S < 0 or H
+ * outside 1 .. 4096.
+ * PN_ERR_ARG (before any launch) for S < 0, total < 0, H outside 1 .. 4096, refine outside 0 .. 4, min_cos outside [0, 1]
+ * with an axis, S * H >= 2^31, a NULL pts, off, threshold, plane, count, best, inlier or ws, or a workspace that is too
+ * small; S == 0 or total == 0 returns 0 without a launch and writes nothing. */
+long long pn_plane_workspace_bytes(long long total, int S, int H);
+int pn_plane_launches(int refine);
+int pn_plane_f32(const float* pts, const int* off, int S, int total, const float* threshold, int H, long long seed,
+                 int refine, const double* axis, double min_cos, double* plane, int32_t* count, int32_t* best,
+                 uint8_t* inlier, float* dist, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

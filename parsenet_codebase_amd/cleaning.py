@@ -36,7 +36,26 @@ density the network was trained at:
 
 Limits of the clusters.  A radius far above the point spacing costs the points in the ball per point and round.  Two
 objects that touch (closer than the radius anywhere) are one component.  A label -1 means "dropped" (a component below
-min_size), not "outlier"."""
+min_size), not "outlier".
+
+Parts lie on a table, a floor or a fixture plate, every part touches that plane, and the plane links them all into one
+component.  ``fit_plane`` finds the dominant plane of a cloud by RANSAC (csrc/plane_math.h, exact and
+bit-reproducible; csrc/plane.hip scores every hypothesis against every point), ``remove_plane`` takes it out — or
+hands it out — and ``peel_planes`` takes several, the largest first.  The tabletop recipe:
+
+    remove_outliers → remove_plane → split_clusters → per object: voxel_downsample → reduce_cloud → network → lift → restore
+
+    pts, nrm, index_o = remove_outliers(scan, normals, search="auto")
+    pts, nrm, index_p, plane = remove_plane(pts, nrm, threshold=2 * noise, axis=(0, 0, 1), max_angle=10)
+    for pts_c, nrm_c, index_c in split_clusters(pts, nrm, radius=3 * spacing, min_size=50):
+        ...                                                              # the pipeline above on pts_c
+        labels = restore(restore(restore(labels_c, index_c, len(pts), -1), index_p, len(index_o), -1), index_o, n, -1)
+
+Limits of the planes.  RANSAC finds the plane with the MOST inliers, not "the floor": a wall that holds more points
+wins unless ``axis`` and ``max_angle`` say which normals count.  A curved surface of low curvature (a large cylinder, a
+shallow dome) can hold more points within the threshold than a small plane and win against it.  A threshold below the
+sensor noise splits one plane in two: the first takes a slab of it, ``peel_planes`` finds the rest as a second plane.
+The cost is hypotheses x points, whatever the cloud looks like; there is no early exit."""
 import math
 import numbers
 
@@ -246,6 +265,119 @@ def keep_largest(points, *per_point, radius):
     res = [[a[p] for p in picked] for a in (clouds.flat,) + beside]
     res.append([p - o for p, o in zip(picked, clouds.off[:-1].tolist())])
     return tuple(part[0] if clouds.layout == "single" else part for part in res)
+
+
+def _plane_arguments(points, threshold, who):
+    """The threshold check of the plane functions, before anything touches the GPU -> (S,) fp32 on the host."""
+    if isinstance(points, (list, tuple)):
+        S = len(points)
+    else:
+        S = int(points.shape[0]) if torch.is_tensor(points) and points.dim() == 3 else 1
+    return _positive_per_cloud(threshold, S, who, "threshold", "number")
+
+
+def _fit(clouds, thresholds, hypotheses, seed, refine, axis, max_angle, want):
+    return K.plane_ragged(clouds.flat, clouds, _lib.h2d(thresholds, clouds.flat.device), hypotheses, seed, refine, axis,
+                          max_angle, want=want)
+
+
+def fit_plane(points, threshold, hypotheses=512, seed=0, refine=1, axis=None, max_angle=None, return_info=False):
+    """The dominant plane of every cloud — the table, the floor, the fixture plate — by RANSAC (PCL's
+    SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, open3d's segment_plane).
+
+    points: (N,3) or (B,N,3) fp32 on the GPU, or a list of (N_b,3) tensors (a ragged batch).
+    threshold: a positive finite number, or one per cloud (host numbers, as the radius of ``euclidean_clusters``): a
+       point belongs to a plane when it is no further from it than this.  The sensor noise sets it.
+    hypotheses: 1 .. 4096 planes through three points of the cloud are tried; seed: an integer, which fixes the draws.
+    refine: 0 .. 4 rounds of a least-squares plane through the inliers; a round is taken only if it loses no inlier.
+    axis, max_angle: three numbers and degrees 0 .. 90, together or not at all: only planes whose normal is within
+       max_angle of +-axis are considered (axis=(0,0,1), max_angle=10: the floor, not the wall).
+    Returns (plane, inlier): plane fp64, (4,), (B,4) or a list of (4,): nx, ny, nz, d with n . p + d = 0, |n| = 1 and
+    the component of n of largest magnitude positive; inlier, a bool mask in the layout of the points.  With
+    ``return_info`` a tuple (plane, inlier, count, best, dist): count int32, a scalar, (B,) or a list: the inliers, -1
+    for a cloud that holds a non-finite coordinate; best int32 likewise: the winning hypothesis, -1 where none is valid
+    (fewer than three points, a collinear cloud, an axis that excludes every sample: plane zeros, no inlier, dist NaN);
+    dist fp32 in the layout of the points: the signed distance of every point to the plane.
+    All results are functions of the cloud and the arguments alone (csrc/plane_math.h), the same bits from run to run
+    and for every batching.  One ``kernels.plane_ragged`` call, no host synchronisation."""
+    who = "fit_plane"
+    thresholds = _plane_arguments(points, threshold, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    out = _fit(clouds, thresholds, hypotheses, seed, refine, axis, max_angle, ("dist",) if return_info else ())
+    plane, inlier = clouds.per_cloud(out[0]), clouds.per_point(out[3])
+    if not return_info:
+        return plane, inlier
+    return plane, inlier, clouds.per_cloud(out[1]), clouds.per_cloud(out[2]), clouds.per_point(out[4])
+
+
+def remove_plane(points, *per_point, threshold, keep="rest", hypotheses=512, seed=0, refine=1, axis=None,
+                 max_angle=None):
+    """Take the dominant plane out of a scan: (points[index], *[a[index] for a in per_point], index, plane).
+
+    points, threshold, hypotheses, seed, refine, axis, max_angle: as in ``fit_plane``.  per_point: arrays with one row
+    per point in the layout of ``points``.  keep: "rest" — everything but the inliers of the plane — or "plane" — the
+    inliers.  ``index``, int64, holds per cloud the original row of every point handed out, ascending — keep it for
+    ``restore``; ``plane`` is the plane of ``fit_plane``.  A single cloud comes back as tensors; a batch or a list comes
+    back as LISTS of tensors, one per cloud.  A cloud that holds a non-finite coordinate, or in which no hypothesis is
+    valid, has no plane: it keeps all its points under "rest" and none under "plane".
+    Exactly one host read: the inlier counts of the clouds, which size the results."""
+    who = "remove_plane"
+    if keep not in ("rest", "plane"):
+        raise ValueError('%s: keep must be "rest" or "plane", got %r' % (who, keep))
+    thresholds = _plane_arguments(points, threshold, who)
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    beside = tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    plane, count, _, inlier = _fit(clouds, thresholds, hypotheses, seed, refine, axis, max_angle, ())
+    host = _read_counts(count)
+    for c, v in enumerate(host):
+        if v == -2:
+            raise ValueError("%s: cloud %d: threshold = %r is no positive finite fp32 number"
+                             % (who, c, float(thresholds[c])))
+    found = [max(v, 0) for v in host]
+    counts = found if keep == "plane" else [n - m for n, m in zip(clouds.sizes, found)]
+    # a stable sort by "handed out first" keeps the rows ascending, cloud after cloud
+    last = (inlier if keep == "rest" else ~inlier).to(torch.uint8)
+    rows = torch.sort(last, stable=True).indices[:sum(counts)]
+    base = clouds.off[:-1].tolist()
+    res = [a[rows] if clouds.layout == "single" else list(torch.split(a[rows], counts))
+           for a in (clouds.flat,) + beside]
+    local = [r - o for r, o in zip(torch.split(rows, counts), base)]
+    return tuple(res) + (local[0] if clouds.layout == "single" else local, clouds.per_cloud(plane))
+
+
+def peel_planes(points, *per_point, threshold, max_planes, min_inliers, hypotheses=512, seed=0, refine=1, axis=None,
+                max_angle=None):
+    """The planes of ONE cloud, the largest first: ``remove_plane`` on what is left, up to ``max_planes`` times.
+
+    points (N,3) and per_point (N,...): one cloud.  It stops at the first plane with fewer than ``min_inliers`` inliers
+    (an integer >= 1), which is not handed out; round p uses seed + p.  The other arguments as in ``fit_plane``.
+    Returns (planes, rest): planes, a list of (points_p, *per_point_p, index_p, plane_p), and rest, (points_r,
+    *per_point_r, index_r): what no plane took.  Every index, int64 ascending, refers to the ORIGINAL rows; the indices
+    are disjoint and together hold every row.
+    One host read per plane tried (the inlier count, inside ``remove_plane``)."""
+    who = "peel_planes"
+    if not torch.is_tensor(points) or points.dim() != 2:
+        raise ValueError("%s: one cloud (N,3)" % who)
+    for name, v in (("max_planes", max_planes), ("min_inliers", min_inliers)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v < 2 ** 31:
+            raise ValueError("%s: %s must be an integer >= 1, got %r" % (who, name, v))
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+        raise ValueError("%s: seed must be an integer, got %r" % (who, seed))
+    clouds = Clouds(points, who, bad_dtype=TypeError)
+    left = (clouds.flat,) + tuple(clouds.beside(a, who, "a per-point array") for a in per_point)
+    origin = torch.arange(clouds.total, dtype=torch.int64, device=clouds.flat.device)
+    planes = []
+    for p in range(int(max_planes)):
+        out = remove_plane(*left, origin, threshold=threshold, keep="plane", hypotheses=hypotheses,
+                           seed=(seed + p) & (2 ** 64 - 1), refine=refine, axis=axis, max_angle=max_angle)
+        local = out[-2]
+        if local.shape[0] < min_inliers:
+            break
+        planes.append(tuple(out[:-3]) + (out[-3], out[-1]))
+        rest = torch.ones(left[0].shape[0], dtype=torch.bool, device=local.device)
+        rest[local] = False
+        left, origin = tuple(a[rest] for a in left), origin[rest]
+    return planes, left + (origin,)
 
 
 def restore(values, index, n, fill):

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI.  Each function validates layout, allocates
 outputs/workspace through torch's caching allocator and launches on torch's current
 HIP stream.  No arithmetic happens here."""
+import math
 import numbers
 
 import numpy as np
@@ -473,6 +474,96 @@ def cluster_ragged(pts, off, radius, min_size=1, want=CLUSTER_OUTPUTS):
                                     ptr(ws), wsz, current_stream(dev))
         check(rc, "pn_cluster_f32")
     return (label, ncomp) + tuple(out[name] for name in CLUSTER_OUTPUTS if name in want)
+
+
+PLANE_OUTPUTS = ("dist",)
+PLANE_MAX_H, PLANE_MAX_REFINE = 4096, 4
+
+
+def _plane_axis(who, axis, max_angle):
+    """axis and max_angle of ``plane_ragged`` -> (None, 0.0) or (the unit axis as three fp64 numbers, min_cos)."""
+    if (axis is None) != (max_angle is None):
+        raise ValueError("%s: axis and max_angle come together, got axis=%r, max_angle=%r" % (who, axis, max_angle))
+    if axis is None:
+        return None, 0.0
+    try:
+        a = [float(v) for v in axis]
+    except (TypeError, ValueError):
+        raise ValueError("%s: axis must be three numbers, got %r" % (who, axis))
+    if len(a) != 3 or any(isinstance(v, bool) for v in axis):
+        raise ValueError("%s: axis must be three numbers, got %r" % (who, axis))
+    a = np.asarray(a, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        length = np.sqrt((a * a).sum())
+    if not (np.isfinite(a).all() and np.isfinite(length) and length > 0.0):
+        raise ValueError("%s: axis must be finite and not zero, got %r" % (who, axis))
+    if isinstance(max_angle, bool) or not isinstance(max_angle, numbers.Real) or not 0.0 <= max_angle <= 90.0:
+        raise ValueError("%s: max_angle must be a number of degrees 0 .. 90, got %r" % (who, max_angle))
+    min_cos = min(1.0, max(0.0, math.cos(math.radians(float(max_angle)))))
+    return np.ascontiguousarray(a / length), min_cos
+
+
+def plane_ragged(pts, off, threshold, hypotheses=512, seed=0, refine=1, axis=None, max_angle=None, want=PLANE_OUTPUTS):
+    """The dominant plane of every segment of a ragged batch (csrc/plane.hip, definition csrc/plane_math.h), exact and
+    bit-reproducible.  pts (total,3) fp32, off (S+1) int32 device offsets or a ``ragged.Clouds``, threshold (S,) fp32
+    on the device: a point is an inlier of a plane (n, d) iff |n . p + d| <= t in fp64; hypotheses 1 .. 4096 planes
+    through three points drawn by a hash of (seed, h); refine 0 .. 4 rounds of a least-squares plane through the
+    inliers, each taken only if it loses no inlier; axis (three host numbers, normalised here in fp64) with max_angle
+    (degrees, 0 .. 90): only planes whose normal lies within max_angle of +-axis count; ``want``: () or ("dist",).
+    Returns (plane (S,4) fp64: nx, ny, nz, d with |n| = 1 and the component of largest magnitude positive; count (S,)
+    int32, the inliers; best (S,) int32, the winning hypothesis; inlier (total,) bool) and, with "dist" in ``want``, dist
+    (total,) fp32, the signed distance of every point to the plane of its segment.  best -1: no valid hypothesis (fewer
+    than three points, a collinear cloud, an axis that excludes every sample): count 0, plane zeros, no inlier, dist NaN.
+    count -1: the segment holds a non-finite coordinate; -2: its threshold is no positive finite number; both as best -1.
+    ``pn_plane_launches(refine)`` = 5 + 6 refine stream-ordered launches on a workspace allocated here, no host
+    synchronisation."""
+    who = "plane_ragged"
+    if not torch.is_tensor(threshold):
+        raise TypeError("%s: threshold must be a tensor, got %s" % (who, type(threshold).__name__))
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, numbers.Integral) or not 1 <= hypotheses <= PLANE_MAX_H:
+        raise ValueError("%s: hypotheses must be an integer 1 .. %d, got %r" % (who, PLANE_MAX_H, hypotheses))
+    if isinstance(refine, bool) or not isinstance(refine, numbers.Integral) or not 0 <= refine <= PLANE_MAX_REFINE:
+        raise ValueError("%s: refine must be an integer 0 .. %d, got %r" % (who, PLANE_MAX_REFINE, refine))
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not -2 ** 63 <= seed < 2 ** 64:
+        raise ValueError("%s: seed must be an integer of 64 bits, got %r" % (who, seed))
+    axis, min_cos = _plane_axis(who, axis, max_angle)
+    unknown = [w for w in want if w not in PLANE_OUTPUTS]
+    if unknown:
+        raise ValueError("%s: want holds %s, got %r" % (who, ", ".join(PLANE_OUTPUTS), unknown))
+    for t in (pts, threshold) + (() if isinstance(off, Clouds) else (off,)):
+        if torch.is_tensor(t) and not t.is_cuda:
+            raise TypeError("%s: pts, off and threshold must be on the GPU, got a %s tensor" % (who, t.device))
+    pts, upload, S, _ = _device_offsets(who, pts, off, 0)
+    total, S, dev = pts.shape[0], max(S, 0), pts.device
+    if total >= 2 ** 31:
+        raise ValueError("%s: total = %d (below 2^31)" % (who, total))
+    if S * int(hypotheses) >= 2 ** 31:
+        raise ValueError("%s: segments * hypotheses = %d (below 2^31)" % (who, S * int(hypotheses)))
+    threshold = _f32c(threshold, "threshold")
+    if tuple(threshold.shape) != (S,) or threshold.device != dev:
+        raise ValueError("%s: threshold must be (%d,) on %s, got %s on %s" % (who, S, dev, tuple(threshold.shape),
+                                                                              threshold.device))
+    inlier = torch.empty(total, dtype=torch.bool, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev) if "dist" in want else None
+    if total == 0 or S == 0:                          # nothing to launch: every segment is empty
+        plane = torch.zeros((S, 4), dtype=torch.float64, device=dev)
+        count = torch.where((threshold > 0) & torch.isfinite(threshold), 0, -2).to(torch.int32)
+        best = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    else:
+        plane = torch.empty((S, 4), dtype=torch.float64, device=dev)
+        count = torch.empty(S, dtype=torch.int32, device=dev)
+        best = torch.empty(S, dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        wsz = lib.pn_plane_workspace_bytes(total, S, int(hypotheses))
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        seed64 = int(seed) & (2 ** 64 - 1)
+        with _lib.on_device(dev):
+            rc = lib.pn_plane_f32(ptr(pts), ptr(upload()), S, total, ptr(threshold), int(hypotheses),
+                                  seed64 - 2 ** 64 if seed64 >= 2 ** 63 else seed64, int(refine),
+                                  None if axis is None else axis.ctypes.data, float(min_cos), ptr(plane), ptr(count),
+                                  ptr(best), ptr(inlier), ptr(dist), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_plane_f32")
+    return (plane, count, best, inlier) + ((dist,) if "dist" in want else ())
 
 
 OUTLIER_MIN_K, OUTLIER_MAX_K = 1, 64
