@@ -1049,6 +1049,52 @@ int pn_plane_f32(const float* pts, const int* off, int S, int total, const float
                  int refine, const double* axis, double min_cos, double* plane, int32_t* count, int32_t* best,
                  uint8_t* inlier, float* dist, void* ws, long long ws_bytes, void* stream);
 
+/* ---- exact neighbours ACROSS two clouds of any size (csrc/knn3_query.hip; grid, cells and bound: csrc/knn3_grid_math.h,
+ * build phases and ring loop shared with csrc/knn3_grid.hip through csrc/knn3_grid_build.h) -----------------------------
+ * ref (totalR,3) and qry (totalQ,3) fp32, off_r and off_q (S+1) DEVICE int32 row offsets from 0 to totalR / totalQ:
+ * segment s of the queries is searched in segment s of the reference.  For query i the result is the k smallest
+ * reference points of its segment under the key (d, j) ascending, d = ((x_i-x_j)^2 + (y_i-y_j)^2) + (z_i-z_j)^2, every
+ * operation rounded once in fp32, no fma (kg_dist, the expression of pn_knn3_grid_f32), j the index LOCAL to the
+ * reference segment.  idx (totalQ,k) int32; dist (totalQ,k) fp32 or NULL: (float) sqrt((double) d).
+ *   A reference segment of n_r < k points: idx -1, dist +inf from entry n_r on (an empty one: in every entry).
+ *   A reference segment that holds a non-finite coordinate: idx -1, dist NaN in every row of its queries.
+ *   A query with a non-finite coordinate: idx -1, dist NaN in that row alone (whatever its reference holds).
+ *   A row of qry that no valid segment holds (or whose reference segment does not lie inside 0 .. totalR): -1, NaN.
+ * 1 <= k <= 64, any sizes with totalQ * k < 2^31.  All outputs are functions of the inputs alone: the same bits from run
+ * to run and for every batching.
+ * pn_knn3_query_launches() = 8 stream-ordered kernel launches (four memsets come on top); it needs no GPU: bounding
+ * boxes, cells, scan and scatter of the reference; the queries' cells in the reference's grid, scan and scatter of the
+ * queries into that cell order; the search, one wave per query, the row written to the query's original position.  No
+ * host synchronisation, no cooperative launch, no waiting between workgroups.  Workspace of
+ * pn_knn3_query_workspace_bytes(totalR, totalQ, S) bytes, linear in both totals: 32 totalR + 12 totalQ + 44 S + 16
+ * (0 for a negative argument).
+ * PN_ERR_ARG (before any launch) for k out of range, S < 0, totalR < 0, totalQ < 0, totalQ * k >= 2^31, a NULL off_r,
+ * qry, off_q, idx or ws, a NULL ref with totalR > 0, or a workspace that is too small; S == 0 or totalQ == 0 returns 0
+ * without a launch; totalR == 0 with queries writes the empty-reference rows in one launch. */
+long long pn_knn3_query_workspace_bytes(long long totalR, long long totalQ, int S);
+int pn_knn3_query_launches(void);
+int pn_knn3_query_f32(const float* ref, const int* off_r, int totalR, const float* qry, const int* off_q, int totalQ,
+                      int S, int k, int32_t* idx, float* dist, void* ws, long long ws_bytes, void* stream);
+
+/* ---- k-nearest-sample lifting: per-sample values carried to every point (csrc/knn_lift.hip, definition:
+ * csrc/knn_lift_math.h) -------------------------------------------------------------------------------------------------
+ * idx, dist (totalQ,k): what pn_knn3_query_f32 wrote for the same off_r, off_q, S and k; an entry is valid when
+ * 0 <= idx < n_r of its segment.  One launch each, no workspace, no host synchronisation.
+ * pn_knn_interpolate_f32: values (totalR,C) fp32, out (totalQ,C) fp32, C >= 1.  w_j = 1.0 / ((double) dist_j + 1e-8)
+ * (PointNet++'s three_interpolate), out_c = (float) ((SUM_j w_j v_jc) / (SUM_j w_j)) over the valid entries in ascending
+ * rank, both sums in fp64 from 0.0, every operation rounded once, no fma.  A row with no valid entry or with a NaN in
+ * dist, and a row that no valid segment holds, is NaN in every channel.  totalQ * C < 2^39.
+ * pn_knn_vote_i32: labels (totalR) int32, out (totalQ) int32: the label that occurs most often among the valid entries
+ * with a label >= 0, on equal counts the one whose first occurrence has the lowest rank; none, or a row that no valid
+ * segment holds: -1.  Integer arithmetic only.
+ * PN_ERR_ARG (before any launch) for k < 1 or k > 64, S < 0, totalR < 0, totalQ < 0, totalQ * k >= 2^31, C < 1,
+ * totalQ * C >= 2^39, a NULL off_r, idx, dist (interpolate), off_q or out, or a NULL values / labels with totalR > 0;
+ * S == 0 or totalQ == 0 returns 0 without a launch. */
+int pn_knn_interpolate_f32(const float* values, const int* off_r, int totalR, const int32_t* idx, const float* dist,
+                           const int* off_q, int totalQ, int S, int k, int C, float* out, void* stream);
+int pn_knn_vote_i32(const int32_t* labels, const int* off_r, int totalR, const int32_t* idx, const int* off_q,
+                    int totalQ, int S, int k, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,9 @@ hands it out — and ``peel_planes`` takes several, the largest first.  The tabl
 
     remove_outliers → remove_plane → split_clusters → per object: voxel_downsample → reduce_cloud → network → lift → restore
 
+(``neighbors.lift_knn(values, pts_c, reduced)`` in place of the ``lift``s: the k nearest samples instead of the one owner,
+smooth along segment boundaries, and it also serves points that were never reduced — the strays, a second scan.)
+
     pts, nrm, index_o = remove_outliers(scan, normals, search="auto")
     pts, nrm, index_p, plane = remove_plane(pts, nrm, threshold=2 * noise, axis=(0, 0, 1), max_angle=10)
     for pts_c, nrm_c, index_c in split_clusters(pts, nrm, radius=3 * spacing, min_size=50):

@@ -3,7 +3,8 @@
 // limit of 10 240 points per cloud.  The definition — grid, cell function, rings, the termination bound and why it is
 // safe — is knn3_grid_math.h, the same source the test suite compiles for the host.
 //
-// Five stream-ordered phases (plus two memsets), no cooperative launch, no grid-wide barrier, no host synchronisation:
+// Five stream-ordered phases (plus two memsets), no cooperative launch, no grid-wide barrier, no host synchronisation.
+// Phases 1 - 4, the workspace and the ring loop of phase 5 are knn3_grid_build.h, shared with knn3_query.hip:
 //   1 bbox     min / max per axis and segment (atomics on the order-preserving integer image, one set per wave where
 //              the wave's rows lie in one segment) and the non-finite flag.  Every later phase derives the segment's
 //              grid from these six numbers with kg_grid: no table is built, nothing is downloaded.
@@ -26,222 +27,10 @@
 //   pn_knn3_grid_search_kernel  VGPRs: 67  TotalSGPRs: 97  ScratchSize [bytes/lane]: 0  Occupancy [waves/SIMD]: 7
 //                               LDS Size [bytes/block]: 0 — no spill
 //   bbox 23 / cells 26 / scan 35 / scatter 12 VGPRs, ScratchSize 0 for all four, 8 waves/SIMD
-#include <stdlib.h>
-
-#include "knn3_grid_math.h"
-#include "knn_common.h"
-#include "ragged.h"
-
-#define KG_ROWS_PER_WAVE 512      // bbox: rows one wave reduces before its six atomics
-
-struct KgWs {
-  float4* rec;
-  int* pcell;
-  int* prank;
-  uint32_t* bmax;      // (S,3) ord of the maxima            } one memset 0
-  uint32_t* flag;      // (S)                                 }
-  int* start;          // (total + 2 S) histogram, then starts }
-  uint32_t* bmin;      // (S,3) ord of the minima: memset 0xff
-};
-
-// The arrays of the workspace in order, cut from `base` (0: measure only); returns their bytes.
-static long long kg_carve(void* base, long long total, long long S, KgWs* w) {
-  RgCarver c = {(uintptr_t)base, 0};
-  w->rec = c.take<float4>(total);
-  w->pcell = c.take<int>(total);
-  w->prank = c.take<int>(total);
-  w->bmax = c.take<uint32_t>(3 * S);
-  w->flag = c.take<uint32_t>(S);
-  w->start = c.take<int>(total + 2 * S);
-  w->bmin = c.take<uint32_t>(3 * S);
-  return c.bytes;
-}
-
-// The segment of a row: the largest s < S with off[s] <= row.  The caller checks off[s] <= row < off[s + 1].
-__device__ static inline int kg_segment(const int* __restrict__ off, int S, int row) {
-  return rg_row_segment(off, S, row);
-}
-
-__device__ static inline KgGrid kg_segment_grid(const KgWs& w, int s, int n, int ppc) {
-  float lo[3], hi[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = pn_ord2f(w.bmin[3 * s + a]);
-    hi[a] = pn_ord2f(w.bmax[3 * s + a]);
-  }
-  return kg_grid(n, lo, hi, ppc);
-}
-
-__device__ static inline uint32_t kg_wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ static inline uint32_t kg_wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
-// ---- 1: bounding boxes and flags -----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pn_knn3_grid_bbox_kernel(const float* __restrict__ pts,
-                                                                const int* __restrict__ off, int S, int total,
-                                                                KgWs w) {
-  const int lane = threadIdx.x & 63;
-  const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long long first = wave * KG_ROWS_PER_WAVE;
-  if (first >= total) return;
-  const int last = (int)(first + KG_ROWS_PER_WAVE - 1 < total - 1 ? first + KG_ROWS_PER_WAVE - 1 : total - 1);
-  const int s0 = kg_segment(off, S, (int)first), s1 = kg_segment(off, S, last);
-  const bool one = s0 == s1 && off[s0] <= (int)first && last < off[s0 + 1];      // (uniform over the wave)
-  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u}, bad = 0u;
-  for (int row = (int)first + lane; row <= last; row += 64) {
-    uint32_t o[3];
-    uint32_t nf = 0u;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float x = pts[(size_t)row * 3 + a];
-      nf |= kg_finite(x) ? 0u : 1u;
-      o[a] = pn_f2ord(x);
-    }
-    if (one) {
-      bad |= nf;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        mn[a] = o[a] < mn[a] ? o[a] : mn[a];
-        mx[a] = o[a] > mx[a] ? o[a] : mx[a];
-      }
-    } else {
-      const int s = kg_segment(off, S, row);
-      if (row < off[s] || row >= off[s + 1]) continue;      // (offsets that do not cover the rows: no segment)
-      if (nf) atomicOr(&w.flag[s], 1u);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        atomicMin(&w.bmin[3 * s + a], o[a]);
-        atomicMax(&w.bmax[3 * s + a], o[a]);
-      }
-    }
-  }
-  if (!one) return;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    mn[a] = kg_wave_min_u32(mn[a]);
-    mx[a] = kg_wave_max_u32(mx[a]);
-  }
-  bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
-  if (lane == 0) {
-    if (bad) atomicOr(&w.flag[s0], 1u);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      atomicMin(&w.bmin[3 * s0 + a], mn[a]);
-      atomicMax(&w.bmax[3 * s0 + a], mx[a]);
-    }
-  }
-}
-
-// ---- 2: the cell of every point, the histogram and the point's rank in its cell ---------------------------------------
-__global__ __launch_bounds__(256) void pn_knn3_grid_cells_kernel(const float* __restrict__ pts,
-                                                                 const int* __restrict__ off, int S, int total,
-                                                                 int ppc, KgWs w) {
-  const long long row64 = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (row64 >= total) return;
-  const int row = (int)row64;
-  const int s = kg_segment(off, S, row);
-  const int o0 = off[s], n = off[s + 1] - o0;
-  w.pcell[row] = -1;
-  if (row < o0 || row - o0 >= n || w.flag[s]) return;
-  const KgGrid g = kg_segment_grid(w, s, n, ppc);
-  const int cell = kg_cell_index(g, kg_cell(g, 0, pts[(size_t)row * 3]), kg_cell(g, 1, pts[(size_t)row * 3 + 1]),
-                                 kg_cell(g, 2, pts[(size_t)row * 3 + 2]));
-  w.pcell[row] = cell;
-  w.prank[row] = atomicAdd(&w.start[(size_t)o0 + 2 * (size_t)s + cell], 1);      // cell < max(1, n)
-}
-
-// ---- 3: exclusive scan of a segment's histogram to record positions --------------------------------------------------
-__global__ __launch_bounds__(1024) void pn_knn3_grid_scan_kernel(const int* __restrict__ off, int ppc, KgWs w) {
-  __shared__ int s_wave[16];
-  __shared__ int s_carry;
-  const int s = blockIdx.x;
-  const int o0 = off[s], n = off[s + 1] - o0;
-  if (n <= 0 || w.flag[s]) return;
-  const KgGrid g = kg_segment_grid(w, s, n, ppc);
-  const int ncell = kg_cells(g);                                     // <= n
-  int* __restrict__ st = w.start + (size_t)o0 + 2 * (size_t)s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = o0;
-  __syncthreads();
-  for (int base = 0; base < ncell; base += 4096) {
-    const int c0 = base + 4 * (int)threadIdx.x;
-    int v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = c0 + e < ncell ? st[c0 + e] : 0;
-    const int mine = (v[0] + v[1]) + (v[2] + v[3]);
-    int inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = s_carry, all = 0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      before += u < wave ? s_wave[u] : 0;
-      all += s_wave[u];
-    }
-    int run = before + inc - mine;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (c0 + e < ncell) st[c0 + e] = run;
-      run += v[e];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry += all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) st[ncell] = s_carry;                         // the end of the last cell: off[s + 1]
-}
-
-// ---- 4: the records in cell order ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pn_knn3_grid_scatter_kernel(const float* __restrict__ pts,
-                                                                   const int* __restrict__ off, int S, int total,
-                                                                   KgWs w) {
-  const long long row64 = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (row64 >= total) return;
-  const int row = (int)row64;
-  const int cell = w.pcell[row];
-  if (cell < 0) return;
-  const int s = kg_segment(off, S, row);
-  const int o0 = off[s], o1 = off[s + 1];
-  const int pos = w.start[(size_t)o0 + 2 * (size_t)s + cell] + w.prank[row];
-  if (pos < o0 || pos >= o1) return;                                 // (cannot happen; never write out of the segment)
-  w.rec[pos] = make_float4(pts[(size_t)row * 3], pts[(size_t)row * 3 + 1], pts[(size_t)row * 3 + 2],
-                           __int_as_float(row - o0));
-}
+#include "knn3_grid_build.h"
 
 // ---- 5: the search --------------------------------------------------------------------------------------------------------
-// One batch: the records [p, min(p + 64, end)) against the wave's list.
-__device__ static inline void kg_batch(const float4* __restrict__ rec, int p, int end, float qx, float qy, float qz,
-                                       int n, int k, u64& best, u64& kth) {
-  const int lane = threadIdx.x & 63;
-  u64 key = 0ull;
-  if (p + lane < end) {
-    const float4 c = rec[p + lane];
-    const int j = __float_as_int(c.w);
-    if ((unsigned)j < (unsigned)n) key = knn_key(-kg_dist(qx, qy, qz, c.x, c.y, c.z), j);
-  }
-  if (__ballot(key > kth) == 0ull) return;
-  knn_wave_sort128(best, key);
-  kth = readlane_u64(best, k - 1);
-}
-
+// (phases 1 - 4, the workspace and the ring loop: knn3_grid_build.h, shared with knn3_query.hip)
 __global__ __launch_bounds__(256) void pn_knn3_grid_search_kernel(const int* __restrict__ off, int S, int total, int k,
                                                                   int ppc, KgWs w, int* __restrict__ idx,
                                                                   float* __restrict__ dist) {
@@ -267,69 +56,12 @@ __global__ __launch_bounds__(256) void pn_knn3_grid_search_kernel(const int* __r
   int c[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) c[a] = kg_cell(g, a, q[a]);
-  const int* __restrict__ st = w.start + (size_t)o0 + 2 * (size_t)s;
-  const int rmax = max(g.dim[0], max(g.dim[1], g.dim[2]));      // the cube of ring rmax covers any grid
-  u64 best = 0ull, kth = 0ull;
-  for (int r = 0; r <= rmax; ++r) {
-    // the rows (y, z) of the shell, clipped to the grid; a row on the rim of the square contributes its whole x range,
-    // a row inside it the two cells at x = c - r and x = c + r
-    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.dim[1] - 1);
-    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.dim[2] - 1);
-    const int ny = y1 - y0 + 1, rows = ny * (z1 - z0 + 1);
-    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.dim[0] - 1);
-    for (int t0 = 0; t0 < rows; t0 += 64) {
-      int b0 = 0, e0 = 0, b1 = 0, e1 = 0;
-      const int t = t0 + lane;
-      if (t < rows) {
-        const int y = y0 + t % ny, z = z0 + t / ny;
-        const int row = (z * g.dim[1] + y) * g.dim[0];
-        const int dy = y - c[1], dz = z - c[2];
-        if (max(dy < 0 ? -dy : dy, dz < 0 ? -dz : dz) == r) {
-          b0 = st[row + x0];
-          e0 = st[row + x1 + 1];
-        } else {
-          if (c[0] - r >= 0) {
-            b0 = st[row + c[0] - r];
-            e0 = st[row + c[0] - r + 1];
-          }
-          if (c[0] + r <= g.dim[0] - 1) {
-            b1 = st[row + c[0] + r];
-            e1 = st[row + c[0] + r + 1];
-          }
-        }
-        b0 = max(b0, o0);      // (a range never leaves the segment's records, whatever the table holds)
-        e0 = min(e0, o1);
-        b1 = max(b1, o0);
-        e1 = min(e1, o1);
-      }
-      u64 m = __ballot(e0 > b0);
-      while (m) {
-        const int l = __builtin_ctzll(m);
-        m &= m - 1;
-        const int b = __builtin_amdgcn_readlane(b0, l), e = __builtin_amdgcn_readlane(e0, l);
-        for (int pp = b; pp < e; pp += 64) kg_batch(w.rec, pp, e, q[0], q[1], q[2], n, k, best, kth);
-      }
-      m = __ballot(e1 > b1);
-      while (m) {
-        const int l = __builtin_ctzll(m);
-        m &= m - 1;
-        const int b = __builtin_amdgcn_readlane(b1, l), e = __builtin_amdgcn_readlane(e1, l);
-        for (int pp = b; pp < e; pp += 64) kg_batch(w.rec, pp, e, q[0], q[1], q[2], n, k, best, kth);
-      }
-    }
-    if (kg_covers(g, c, r)) break;
-    if (kth == 0ull) continue;                                     // fewer than k candidates so far
-    const float dk = fabsf(pn_ord2f((uint32_t)(kth >> 32)));      // the key holds -d: |.| gives d, and +0 for d = 0
-    if (dk < kg_bound(g, c, r, q)) break;                          // (uniform over the wave)
-  }
+  const u64 best = kg_ring_search(w, w.start + (size_t)o0 + 2 * (size_t)s, g, o0, o1, n, k, q, c);
   if (lane < k) {
     const size_t o = ((size_t)o0 + self) * k + lane;
     const bool have = best != 0ull;                                // fewer than k points in the segment: pad with self
     idx[o] = have ? (int)knn_key_index(best) : self;
-    if (dist) {
-      const float d = have ? fabsf(pn_ord2f((uint32_t)(best >> 32))) : 0.0f;
-      dist[o] = (float)sqrt((double)d);
-    }
+    if (dist) dist[o] = have ? kg_key_dist(best) : 0.0f;
   }
 }
 
@@ -338,13 +70,6 @@ extern "C" long long pn_knn3_grid_workspace_bytes(long long total, int S) {
   if (total < 0 || S < 0) return 0;
   KgWs w;
   return kg_carve(nullptr, total, S, &w) + 16;
-}
-
-// PN_KNN3_GRID_PPC: developer hook of tools/knn3_grid_ab.py — the points per cell, which moves the speed and no output.
-static int kg_ppc(void) {
-  const char* e = getenv("PN_KNN3_GRID_PPC");
-  const int v = e ? atoi(e) : 0;
-  return v >= 1 && v <= KG_MAX_PPC ? v : KG_PPC;
 }
 
 extern "C" int pn_knn3_grid_f32(const float* pts, const int* off, int S, int total, int max_n, int k, int32_t* idx,
@@ -361,27 +86,8 @@ extern "C" int pn_knn3_grid_f32(const float* pts, const int* off, int S, int tot
   KgWs w;
   kg_carve((void*)pn_align_up((size_t)ws, 16), total, S, &w);
   const int ppc = kg_ppc();
-  const size_t zero_bytes = (size_t)((char*)w.bmin - (char*)w.bmax);      // box max, flag and cell starts
-  PN_CHECK_HIP(hipMemsetAsync(w.bmax, 0, zero_bytes, stream));
-  PN_CHECK_HIP(hipMemsetAsync(w.bmin, 0xff, (size_t)12 * S, stream));
-  const int row_blocks = pn_cdiv(total, 256);
-  {
-    PN_PROF("knn3_grid_bbox", stream);
-    hipLaunchKernelGGL(pn_knn3_grid_bbox_kernel, dim3(pn_cdiv(total, 4 * KG_ROWS_PER_WAVE)), dim3(256), 0, stream, pts,
-                       off, S, total, w);
-  }
-  {
-    PN_PROF("knn3_grid_cells", stream);
-    hipLaunchKernelGGL(pn_knn3_grid_cells_kernel, dim3(row_blocks), dim3(256), 0, stream, pts, off, S, total, ppc, w);
-  }
-  {
-    PN_PROF("knn3_grid_scan", stream);
-    hipLaunchKernelGGL(pn_knn3_grid_scan_kernel, dim3(S), dim3(1024), 0, stream, off, ppc, w);
-  }
-  {
-    PN_PROF("knn3_grid_scatter", stream);
-    hipLaunchKernelGGL(pn_knn3_grid_scatter_kernel, dim3(row_blocks), dim3(256), 0, stream, pts, off, S, total, w);
-  }
+  const int rc = kg_build_launch(pts, off, S, total, ppc, w, stream);
+  if (rc != PN_OK) return rc;
   {
     PN_PROF("knn3_grid_search", stream);
     hipLaunchKernelGGL(pn_knn3_grid_search_kernel, dim3(pn_cdiv(total, 4)), dim3(256), 0, stream, off, S, total, k, ppc,

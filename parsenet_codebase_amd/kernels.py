@@ -191,6 +191,132 @@ def knn3_grid(pts, off, max_n, k, want_dist=False):
     return (idx, dist) if want_dist else idx
 
 
+QUERY_MIN_K, QUERY_MAX_K = 1, 64
+
+
+def _pair_offsets(who, ref_rows, off_r, qry_rows, off_q, dev):
+    """The offsets of a (reference, query) pair of ragged batches -> (upload_r, upload_q, S).  Each of off_r, off_q is
+    a device int32 tensor or the ``ragged.Clouds`` its rows were flattened by; both must describe S clouds."""
+    ups, Ss = [], []
+    for off, rows, what in ((off_r, ref_rows, "off_r"), (off_q, qry_rows, "off_q")):
+        if isinstance(off, Clouds):
+            if rows != off.total or dev != off.flat.device:
+                raise ValueError("%s: %d rows on %s do not belong to the Clouds given as %s (%d points on %s)"
+                                 % (who, rows, dev, what, off.total, off.flat.device))
+            ups.append(off.device_offsets)
+            Ss.append(off.S)
+        else:
+            require_cuda(off)
+            if off.dtype != torch.int32:
+                raise TypeError("%s: %s must be int32" % (who, what))
+            ups.append(off.contiguous)
+            Ss.append(off.numel() - 1)
+    if Ss[0] != Ss[1]:
+        raise ValueError("%s: off_r describes %d clouds, off_q %d" % (who, Ss[0], Ss[1]))
+    return ups[0], ups[1], max(Ss[0], 0)
+
+
+def _query_k(who, k, rows):
+    k = int(k)
+    if not QUERY_MIN_K <= k <= QUERY_MAX_K:
+        raise ValueError("%s: k must be %d .. %d, got %d" % (who, QUERY_MIN_K, QUERY_MAX_K, k))
+    if rows * k >= 2 ** 31:
+        raise ValueError("%s: totalQ * k = %d (below 2^31)" % (who, rows * k))
+    return k
+
+
+def knn3_query(ref, off_r, qry, off_q, k, want_dist=False):
+    """The k nearest REFERENCE points of every query point, segment s of the queries searched in segment s of the
+    reference (csrc/knn3_query.hip; grid, cells and bound of csrc/knn3_grid_math.h, built on the reference): exact, cost
+    O((n_r + n_q) k), any sizes.  ref (totalR,3), qry (totalQ,3) fp32; off_r, off_q (S+1) int32 device offsets or the
+    ``ragged.Clouds`` the points were flattened by.  Returns idx (totalQ,k) int32 LOCAL to the reference segment — the k
+    smallest under the fp32 ((dx² + dy²) + dz²), equal distances to the smaller index — and, with ``want_dist``, their
+    fp32 distances.  A reference of n_r < k points: idx -1 and dist +inf from entry n_r on.  A non-finite coordinate in
+    the reference segment (every row of its queries) or in the query (that row): idx -1, dist NaN.  1 <= k <= 64,
+    totalQ * k < 2^31.  ``pn_knn3_query_launches()`` = 8 stream-ordered launches on a workspace linear in both totals,
+    no host synchronisation; the same bits from run to run and for every batching."""
+    require_cuda(ref, qry)
+    ref, qry = _f32c(ref, "ref"), _f32c(qry, "qry")
+    for t, what in ((ref, "reference"), (qry, "query")):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("knn3_query expects (total,3) %s points, got %s" % (what, tuple(t.shape)))
+    if ref.device != qry.device:
+        raise ValueError("knn3_query: the reference is on %s, the queries on %s" % (ref.device, qry.device))
+    totalR, totalQ, dev = ref.shape[0], qry.shape[0], qry.device
+    k = _query_k("knn3_query", k, totalQ)
+    up_r, up_q, S = _pair_offsets("knn3_query", totalR, off_r, totalQ, off_q, dev)
+    idx = torch.empty((totalQ, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((totalQ, k), dtype=torch.float32, device=dev) if want_dist else None
+    if totalQ > 0 and S > 0:
+        lib = _lib.load()
+        wsz = lib.pn_knn3_query_workspace_bytes(totalR, totalQ, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_knn3_query_f32(ptr(ref), ptr(up_r()), totalR, ptr(qry), ptr(up_q()), totalQ, S, k, ptr(idx),
+                                       ptr(dist), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_knn3_query_f32")
+    return (idx, dist) if want_dist else idx
+
+
+def _lift_args(who, off_r, totalR, idx, off_q):
+    require_cuda(idx)
+    idx = _i32c(idx, "idx")
+    if idx.dim() != 2:
+        raise ValueError("%s expects (totalQ,k) idx, got %s" % (who, tuple(idx.shape)))
+    totalQ, k = idx.shape
+    k = _query_k(who, k, totalQ)
+    up_r, up_q, S = _pair_offsets(who, totalR, off_r, totalQ, off_q, idx.device)
+    return idx, totalQ, k, up_r, up_q, S
+
+
+def knn_interpolate(values, off_r, idx, dist, off_q):
+    """Inverse-distance interpolation of per-reference-point values at the queries (csrc/knn_lift.hip, definition
+    csrc/knn_lift_math.h; PointNet++'s three_interpolate for any k): values (totalR,C) fp32, idx and dist (totalQ,k) as
+    ``knn3_query`` returned them for the same offsets.  out (totalQ,C) fp32 = (float)(Σ w_j v_j / Σ w_j),
+    w_j = 1 / ((double) dist_j + 1e-8), in fp64 in ascending rank over the entries with idx >= 0.  A row with no such
+    entry or with a NaN distance is NaN.  One launch, no host synchronisation."""
+    require_cuda(values, dist)
+    values, dist = _f32c(values, "values"), _f32c(dist, "dist")
+    if values.dim() != 2 or values.shape[1] < 1:
+        raise ValueError("knn_interpolate expects (totalR,C) values with C >= 1, got %s" % (tuple(values.shape),))
+    totalR, C = values.shape
+    idx, totalQ, k, up_r, up_q, S = _lift_args("knn_interpolate", off_r, totalR, idx, off_q)
+    if dist.shape != idx.shape or dist.device != idx.device or values.device != idx.device:
+        raise ValueError("knn_interpolate: dist %s must have the shape of idx %s, on the device of idx and values"
+                         % (tuple(dist.shape), tuple(idx.shape)))
+    if totalQ * C >= 2 ** 39:
+        raise ValueError("knn_interpolate: totalQ * C = %d (below 2^39)" % (totalQ * C))
+    out = torch.empty((totalQ, C), dtype=torch.float32, device=idx.device)
+    if totalQ > 0 and S > 0:
+        with _lib.on_device(idx.device):
+            rc = _lib.load().pn_knn_interpolate_f32(ptr(values), ptr(up_r()), totalR, ptr(idx), ptr(dist), ptr(up_q()),
+                                                    totalQ, S, k, C, ptr(out), current_stream(idx.device))
+        check(rc, "pn_knn_interpolate_f32")
+    return out
+
+
+def knn_vote(labels, off_r, idx, off_q):
+    """Majority vote of per-reference-point labels at the queries (csrc/knn_lift.hip, definition csrc/knn_lift_math.h):
+    labels (totalR) int32, idx (totalQ,k) as ``knn3_query`` returned it for the same offsets.  out (totalQ) int32: the
+    label >= 0 that occurs most often among the entries with idx >= 0, on equal counts the one with the nearer member;
+    none: -1.  One launch, no host synchronisation."""
+    require_cuda(labels)
+    labels = _i32c(labels, "labels")
+    if labels.dim() != 1:
+        raise ValueError("knn_vote expects (totalR) labels, got %s" % (tuple(labels.shape),))
+    totalR = labels.shape[0]
+    idx, totalQ, k, up_r, up_q, S = _lift_args("knn_vote", off_r, totalR, idx, off_q)
+    if labels.device != idx.device:
+        raise ValueError("knn_vote: labels on %s, idx on %s" % (labels.device, idx.device))
+    out = torch.empty(totalQ, dtype=torch.int32, device=idx.device)
+    if totalQ > 0 and S > 0:
+        with _lib.on_device(idx.device):
+            rc = _lib.load().pn_knn_vote_i32(ptr(labels), ptr(up_r()), totalR, ptr(idx), ptr(up_q()), totalQ, S, k,
+                                             ptr(out), current_stream(idx.device))
+        check(rc, "pn_knn_vote_i32")
+    return out
+
+
 NORMALS_MIN_K, NORMALS_MAX_K = 3, 64
 
 

@@ -15,7 +15,9 @@ distances.  csrc/fps.hip runs it from global memory over many workgroups, so no 
 
 Limits.  The sampling is sequential in m: m + 2 stream-ordered launches.  It picks outliers first: a scan with stray
 points goes through ``cleaning.remove_outliers`` before it.  ``owner`` is the nearest SAMPLE, not a surface projection:
-lifting labels across a thin wall follows Euclidean distance.
+lifting labels across a thin wall follows Euclidean distance.  ``neighbors.lift_knn(values, points, reduced, k=3)`` ends
+the pipeline instead of ``lift`` where segment boundaries should be smooth (the k nearest samples, weighted or voting)
+and for points that were never reduced and so have no ``owner``.
 
 A dense, unevenly sampled scan goes through ``voxel_downsample`` first: one point per occupied cell of a cubic grid
 (csrc/voxel_math.h, csrc/voxel.hip: exact centroids from 64-bit integer sums, seven launches whatever the size), which
