@@ -1095,6 +1095,44 @@ int pn_knn_interpolate_f32(const float* values, const int* off_r, int totalR, co
 int pn_knn_vote_i32(const int32_t* labels, const int* off_r, int totalR, const int32_t* idx, const int* off_q,
                     int totalQ, int S, int k, int32_t* out, void* stream);
 
+/* ---- rigid registration of two scans: ICP on the exact grid search (csrc/register.hip, definition:
+ * csrc/register_math.h; the search: the kernels of pn_knn3_query_f32, csrc/knn3_query_kernels.h) --------------------------
+ * src (totalS,3) the cloud that moves, tgt (totalT,3), normals (totalT,3) or NULL, all fp32; off_s, off_t (S+1) DEVICE
+ * int32 row offsets: segment s of the source is registered onto segment s of the target.  mode 0: point to point (Horn's
+ * quaternion by a 4 x 4 Jacobi), 1: point to plane, linearised (6 x 6 LDL^T; needs normals, their orientation does not
+ * matter).  A pair (moved point, its nearest target point under pn_knn3_query_f32's key, k = 1) is accepted iff
+ * dist <= max_dist in fp32 (+inf: every found pair) and, in mode 1, its normal is finite.  init (S,16) fp64 DEVICE
+ * row-major 4 x 4 starts, or NULL for the identity.  Every sum is the fixed fp64 tree of csrc/outlier_math.h over tiles of
+ * 1 024 source points: all outputs are functions of the segment pair and the arguments alone, the same bits alone, in any
+ * batch and in any batch order.
+ * Outputs per segment: transform (S,16) fp64 row-major 4 x 4 (its rotation derived from a unit quaternion), iterations
+ * int32, status int32 (0 converged: 2 |vec(dq)| <= tol_rot and the step moves the centroid by <= tol_trans; 1 max_iter
+ * reached; 2 fewer than 3 (mode 1: 6) accepted pairs; 3 degenerate solve; 4 non-finite target), count int32 and rmse fp64
+ * (sqrt(SUM dist^2 / count), NaN for count 0) of one more pairing with the final transform; per source point, optional
+ * (NULL): idx int32 LOCAL to the target segment and dist fp32 of that pairing, as pn_knn3_query_f32 defines them.
+ * pn_register_launches(max_iter) = 12 + 9 max_iter stream-ordered kernel launches (0 for max_iter outside 1 .. 256; it
+ * needs no GPU): the grid of the target is built once (4), one init launch, per iteration move, the query's four
+ * launches, mean sums, means, centred sums, solve, and a final evaluation of 7.  The schedule is fixed: no host
+ * synchronisation, no cooperative launch, no waiting between workgroups; the workgroups of a segment that has stopped
+ * exit at its device flag.  Workspace of pn_register_workspace_bytes(totalS, totalT, S) bytes:
+ * pn_knn3_query_workspace_bytes(totalT, totalS, S) + 20 totalS + 236 (totalS / 1024 + S) + 120 S (0 for a negative
+ * argument or a total of 2^31 or more).
+ * PN_ERR_ARG (before any launch) for S < 0, totalS < 0, totalT < 0, mode outside 0 .. 1, mode 1 without normals, max_iter
+ * outside 1 .. 256, max_dist < 0 or NaN, tol_rot or tol_trans < 0 or NaN, a NULL off_s, off_t, transform, iterations,
+ * status, count, rmse or ws, a NULL src with totalS > 0 or tgt with totalT > 0, or a workspace that is too small; S == 0
+ * returns 0 without a launch.
+ * pn_rigid_apply_f32: the move step alone, the same bits: out (totalS,3) fp32 = (float)(((R00 x + R01 y) + R02 z) + t0)
+ * ... in fp64 with R derived from the unit quaternion of transform's (S,16 fp64, DEVICE) rotation block.  One launch;
+ * PN_ERR_ARG for S < 0, totalS < 0 or a NULL pointer; S == 0 or totalS == 0 returns 0 without a launch. */
+long long pn_register_workspace_bytes(long long totalS, long long totalT, int S);
+int pn_register_launches(int max_iter);
+int pn_register_f32(const float* src, const int* off_s, int totalS, const float* tgt, const int* off_t, int totalT,
+                    const float* normals, int S, int mode, float max_dist, int max_iter, double tol_rot,
+                    double tol_trans, const double* init, double* transform, int32_t* iterations, int32_t* status,
+                    int32_t* count, double* rmse, int32_t* idx, float* dist, void* ws, long long ws_bytes, void* stream);
+int pn_rigid_apply_f32(const float* src, const int* off_s, int S, int totalS, const double* transform, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,26 +194,28 @@ def knn3_grid(pts, off, max_n, k, want_dist=False):
 QUERY_MIN_K, QUERY_MAX_K = 1, 64
 
 
+def _cloud_offsets(who, rows, off, what, dev):
+    """The offsets of one ragged batch of ``rows`` rows on ``dev`` -> (upload, S).  ``off`` is a device int32 tensor or
+    the ``ragged.Clouds`` the rows were flattened by."""
+    if isinstance(off, Clouds):
+        if rows != off.total or dev != off.flat.device:
+            raise ValueError("%s: %d rows on %s do not belong to the Clouds given as %s (%d points on %s)"
+                             % (who, rows, dev, what, off.total, off.flat.device))
+        return off.device_offsets, off.S
+    require_cuda(off)
+    if off.dtype != torch.int32:
+        raise TypeError("%s: %s must be int32" % (who, what))
+    return off.contiguous, off.numel() - 1
+
+
 def _pair_offsets(who, ref_rows, off_r, qry_rows, off_q, dev):
     """The offsets of a (reference, query) pair of ragged batches -> (upload_r, upload_q, S).  Each of off_r, off_q is
     a device int32 tensor or the ``ragged.Clouds`` its rows were flattened by; both must describe S clouds."""
-    ups, Ss = [], []
-    for off, rows, what in ((off_r, ref_rows, "off_r"), (off_q, qry_rows, "off_q")):
-        if isinstance(off, Clouds):
-            if rows != off.total or dev != off.flat.device:
-                raise ValueError("%s: %d rows on %s do not belong to the Clouds given as %s (%d points on %s)"
-                                 % (who, rows, dev, what, off.total, off.flat.device))
-            ups.append(off.device_offsets)
-            Ss.append(off.S)
-        else:
-            require_cuda(off)
-            if off.dtype != torch.int32:
-                raise TypeError("%s: %s must be int32" % (who, what))
-            ups.append(off.contiguous)
-            Ss.append(off.numel() - 1)
-    if Ss[0] != Ss[1]:
-        raise ValueError("%s: off_r describes %d clouds, off_q %d" % (who, Ss[0], Ss[1]))
-    return ups[0], ups[1], max(Ss[0], 0)
+    up_r, S_r = _cloud_offsets(who, ref_rows, off_r, "off_r", dev)
+    up_q, S_q = _cloud_offsets(who, qry_rows, off_q, "off_q", dev)
+    if S_r != S_q:
+        raise ValueError("%s: off_r describes %d clouds, off_q %d" % (who, S_r, S_q))
+    return up_r, up_q, max(S_r, 0)
 
 
 def _query_k(who, k, rows):
@@ -314,6 +316,105 @@ def knn_vote(labels, off_r, idx, off_q):
             rc = _lib.load().pn_knn_vote_i32(ptr(labels), ptr(up_r()), totalR, ptr(idx), ptr(up_q()), totalQ, S, k,
                                              ptr(out), current_stream(idx.device))
         check(rc, "pn_knn_vote_i32")
+    return out
+
+
+REGISTER_POINT, REGISTER_PLANE = 0, 1
+REGISTER_MAX_ITER = 256
+
+
+def _nonneg(who, name, v, allow_inf=False):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not v >= 0 or (math.isinf(v) and not allow_inf):
+        raise ValueError("%s: %s must be a number >= 0%s, got %r" % (who, name, " (inf allowed)" if allow_inf else "", v))
+    return float(v)
+
+
+def _rows3(who, t, what):
+    t = _f32c(t, what)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s expects (total,3) %s, got %s" % (who, what, tuple(t.shape)))
+    return t
+
+
+def _transforms(who, T, S, dev, name="transform"):
+    """(S,16) fp64 contiguous on ``dev`` from a (S,4,4) or (S,16) float64 device tensor."""
+    if not torch.is_tensor(T) or T.dtype != torch.float64:
+        raise TypeError("%s: %s must be a float64 tensor" % (who, name))
+    if T.numel() != 16 * S or T.dim() not in (2, 3):
+        raise ValueError("%s: %s must be (%d,4,4), got %s" % (who, name, S, tuple(T.shape)))
+    if T.device != dev:
+        raise ValueError("%s: %s is on %s, the points on %s" % (who, name, T.device, dev))
+    return T.reshape(S, 16).contiguous()
+
+
+def register_ragged(src, off_s, tgt, off_t, max_dist, mode=REGISTER_POINT, normals=None, init=None, max_iter=50,
+                    tol_rot=1e-6, tol_trans=1e-6, want_pairs=False):
+    """Rigid registration of segment s of ``src`` (it moves) onto segment s of ``tgt`` by iterative closest point on the
+    exact grid search of ``knn3_query`` (csrc/register.hip, definition csrc/register_math.h).  src (totalS,3), tgt
+    (totalT,3), normals (totalT,3) or None, fp32; off_s, off_t (S+1) int32 device offsets or the ``ragged.Clouds`` the
+    points were flattened by; init (S,4,4) float64 on the device or None (the identity).  mode REGISTER_POINT or
+    REGISTER_PLANE (needs normals).  Returns transform (S,4,4) float64, iterations, status, count (S) int32, rmse (S)
+    float64 and, with ``want_pairs``, idx (totalS) int32 and dist (totalS) fp32 of the final pairing.
+    ``pn_register_launches(max_iter)`` = 12 + 9 max_iter stream-ordered launches, no host synchronisation; the same
+    bits from run to run and for every batching."""
+    who = "register_ragged"
+    require_cuda(src, tgt, normals)
+    src, tgt = _rows3(who, src, "source points"), _rows3(who, tgt, "target points")
+    if mode not in (REGISTER_POINT, REGISTER_PLANE):
+        raise ValueError("%s: mode must be REGISTER_POINT or REGISTER_PLANE, got %r" % (who, mode))
+    if mode == REGISTER_PLANE and normals is None:
+        raise ValueError("%s: REGISTER_PLANE needs the target's normals" % who)
+    if normals is not None:
+        normals = _rows3(who, normals, "normals")
+        if normals.shape != tgt.shape or normals.device != tgt.device:
+            raise ValueError("%s: normals %s must have the shape and the device of the target %s"
+                             % (who, tuple(normals.shape), tuple(tgt.shape)))
+    if src.device != tgt.device:
+        raise ValueError("%s: the source is on %s, the target on %s" % (who, src.device, tgt.device))
+    max_dist = _nonneg(who, "max_dist", max_dist, allow_inf=True)
+    tol_rot, tol_trans = _nonneg(who, "tol_rot", tol_rot), _nonneg(who, "tol_trans", tol_trans)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, numbers.Integral) or not 1 <= max_iter <= REGISTER_MAX_ITER:
+        raise ValueError("%s: max_iter must be an integer 1 .. %d, got %r" % (who, REGISTER_MAX_ITER, max_iter))
+    totalS, totalT, dev = src.shape[0], tgt.shape[0], src.device
+    up_t, up_s, S = _pair_offsets(who, totalT, off_t, totalS, off_s, dev)
+    if init is not None:
+        init = _transforms(who, init, S, dev, "init")
+    T = torch.empty((S, 4, 4), dtype=torch.float64, device=dev)
+    its, status, count = (torch.empty(S, dtype=torch.int32, device=dev) for _ in range(3))
+    rmse = torch.empty(S, dtype=torch.float64, device=dev)
+    idx = torch.empty(totalS, dtype=torch.int32, device=dev) if want_pairs else None
+    dist = torch.empty(totalS, dtype=torch.float32, device=dev) if want_pairs else None
+    if S > 0:
+        lib = _lib.load()
+        wsz = lib.pn_register_workspace_bytes(totalS, totalT, S)
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = lib.pn_register_f32(ptr(src), ptr(up_s()), totalS, ptr(tgt), ptr(up_t()), totalT,
+                                     ptr(normals) if mode == REGISTER_PLANE else None, S, int(mode), max_dist,
+                                     int(max_iter), tol_rot, tol_trans, ptr(init), ptr(T), ptr(its), ptr(status),
+                                     ptr(count), ptr(rmse), ptr(idx), ptr(dist), ptr(ws), wsz, current_stream(dev))
+        check(rc, "pn_register_f32")
+    out = (T, its, status, count, rmse)
+    return out + (idx, dist) if want_pairs else out
+
+
+def rigid_apply(src, off_s, transform):
+    """The move step of the registration as a call of its own, the same bits (csrc/register.hip): src (totalS,3) fp32,
+    off_s (S+1) int32 device offsets or a ``ragged.Clouds``, transform (S,4,4) float64 on the device.  Returns
+    (totalS,3) fp32: (float)(((R00 x + R01 y) + R02 z) + t0) ... in fp64, R derived from the unit quaternion of the
+    transform's rotation block.  One launch, no host synchronisation."""
+    who = "rigid_apply"
+    require_cuda(src)
+    src = _rows3(who, src, "points")
+    totalS, dev = src.shape[0], src.device
+    up_s, S = _cloud_offsets(who, totalS, off_s, "off_s", dev)
+    S = max(S, 0)
+    T = _transforms(who, transform, S, dev)
+    out = torch.empty_like(src)
+    if S > 0 and totalS > 0:
+        with _lib.on_device(dev):
+            rc = _lib.load().pn_rigid_apply_f32(ptr(src), ptr(up_s()), S, totalS, ptr(T), ptr(out), current_stream(dev))
+        check(rc, "pn_rigid_apply_f32")
     return out
 
 
