@@ -2,7 +2,7 @@
 // graph "no further apart than the radius", numbered by their lowest point, under the definition of cluster_math.h —
 // the same source the test suite compiles for the host.  The neighbour search is the exact uniform-grid search of
 // knn3_grid_math.h (cell function and bound as they stand, the resolution chosen from the radius); the merge is the
-// Boruvka engine of orient_global.hip without the parities.
+// Boruvka engine of orient_global.hip without the parities, on the schedule the two share (boruvka_schedule.h).
 //
 // The grid build is NOT shared with knn3_grid.hip: its four kernels derive the grid from a points-per-cell number,
 // these derive it from the radius of the segment (cl_grid), and they also set up the merge.  knn3_grid.hip is untouched.
@@ -101,32 +101,6 @@ __device__ static inline KgGrid cl_segment_grid(const ClWs& w, int s, int n, flo
   return cl_grid(n, lo, hi, r);
 }
 
-__device__ static inline uint32_t cl_wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ static inline uint32_t cl_wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ static inline unsigned long long cl_wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-    const unsigned long long t = ((unsigned long long)hi << 32) | lo;
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
 // ---- bounding boxes, flags, the segment and the parent of every point ---------------------------------------------------
 __global__ __launch_bounds__(256) void pn_cluster_bounds_kernel(const float* __restrict__ pts,
                                                                 const int* __restrict__ off, int S, int total,
@@ -179,8 +153,8 @@ __global__ __launch_bounds__(256) void pn_cluster_bounds_kernel(const float* __r
   if (!one) return;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    mn[a] = cl_wave_min_u32(mn[a]);
-    mx[a] = cl_wave_max_u32(mx[a]);
+    mn[a] = pn_wave_min_u32(mn[a]);
+    mx[a] = pn_wave_max_u32(mx[a]);
   }
   bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
   if (lane == 0) {
@@ -370,7 +344,7 @@ __global__ __launch_bounds__(256) void pn_cluster_offer_kernel(const int* __rest
     }
     if (cl_stop(g, c, r, q, r2)) break;                              // (uniform over the wave)
   }
-  key = cl_wave_min_u64(key);
+  key = pn_wave_min_u64(key);
   if (lane == 0 && key != CL_NO_ENTRY) {
     unsigned long long* slot = w.best + o0 + ci;
     if (key < *slot) atomicMin(slot, key);

@@ -44,21 +44,13 @@
 //   passes    cl_walk: up to CL_WALK further parents from the word of v (P[v], or H[v] while v still stands as a root
 //             in P with a hook pending: first pass only).  Every word read is a single load of an ancestor in the hooked
 //             forest, whichever of its values a concurrent walk left there: correct under any interleaving.
-// The schedule, fixed by the host from the largest segment max_n alone:
-//   cl_rounds ceil(log2 max_n) + 1.  A component that finds an edge leaving it is merged with at least one other; one
-//             that finds none is a whole connected component of the graph and never finds one again.  So the number of
-//             components that can still find an edge at least halves per round: after ceil(log2 n) rounds it is at
-//             most one, which has no partner.  One more round sees "no entry" and raises no flag.
-//   cl_passes the smallest C with CL_WALK^C >= max_n.  Before the hooks every vertex is at depth <= 1; the hooks of a
-//             round can line the components up in one chain, depth <= n - 1.  A pass takes a vertex at depth d to an
-//             ancestor at least min(d, CL_WALK) levels up (a stale or a fresher word is never lower), and roots do not
-//             move during the passes, so the new depth is at most ceil(d / CL_WALK); after C passes it is at most
-//             ceil((n - 1) / CL_WALK^C) = 1: every vertex points at its root, which the next round's offers need.
+// The schedule, fixed by the host from the largest segment max_n alone, is boruvka_schedule.h (shared with
+// orient_global_math.h): cl_rounds = bv_rounds rounds of offers, hooks and cl_passes = bv_passes compress passes, with
+// the proof of both bounds, the control words and the word a pass reads (cl_word = bv_word).
 //   cl_launches  4 (bounds and init, cells, scan, scatter) + rounds x (offers + hooks + passes) + 3 (sizes, numbers,
 //             labels).
-// A per-round control word any[r] — a root found an entry in round r — lets every launch behind the last merge exit in
-// its first instructions; changed[r][p] does the same for the passes behind the one that moved nothing.
 #pragma once
+#include "boruvka_schedule.h"
 #include "knn3_grid_math.h"
 #if !defined(__clang__) && defined(__GNUC__)
 #pragma GCC push_options
@@ -66,30 +58,20 @@
 #endif
 
 #define CL_HD KG_HD
-#define CL_WALK 64                      // parents a vertex walks per compress pass
-#define CL_NO_HOOK 0xffffffffu          // no parent: a parent is below 2^31 - 1
 #define CL_NO_ENTRY 0xffffffffffffffffull
-#define CL_MAX_ROUNDS 32                // cl_rounds(2^31 - 1)
-#define CL_MAX_PASSES 8                 // > cl_passes(2^31 - 1) = 6
 #define CL_NON_FINITE (-1)
 #define CL_BAD_RADIUS (-2)
-// control words (zeroed before the first launch, the first words of the workspace)
-#define CL_CTRL_ANY 0
-#define CL_CTRL_CHANGED 64
-#define CL_CTRL_WORDS (CL_CTRL_CHANGED + CL_MAX_ROUNDS * CL_MAX_PASSES)
-
-CL_HD int cl_rounds(int max_n) {
-  int r = 0;
-  while (r < 31 && (1ll << r) < (long long)max_n) ++r;
-  return r + 1;
-}
-
-CL_HD int cl_passes(int max_n) {
-  int c = 1;
-  long long reach = CL_WALK;
-  while (reach < (long long)max_n) reach *= CL_WALK, ++c;
-  return c;
-}
+// The shared schedule under the names of this engine, which cluster.hip and the host simulation use.
+#define CL_WALK BV_WALK
+#define CL_NO_HOOK BV_NO_HOOK
+#define CL_MAX_ROUNDS BV_MAX_ROUNDS
+#define CL_MAX_PASSES BV_MAX_PASSES
+#define CL_CTRL_ANY BV_CTRL_ANY
+#define CL_CTRL_CHANGED BV_CTRL_CHANGED
+#define CL_CTRL_WORDS BV_CTRL_WORDS      // the first words of the workspace
+CL_HD int cl_rounds(int max_n) { return bv_rounds(max_n); }
+CL_HD int cl_passes(int max_n) { return bv_passes(max_n); }
+CL_HD uint32_t cl_word(const uint32_t* P, const uint32_t* H, uint32_t x, int first) { return bv_word(P, H, x, first); }
 
 CL_HD int cl_launches(int max_n) { return 4 + cl_rounds(max_n) * (2 + cl_passes(max_n)) + 3; }
 
@@ -175,21 +157,12 @@ CL_HD uint32_t cl_hook(const uint32_t* P, const unsigned long long* best, int n,
   return other;
 }
 
-CL_HD uint32_t cl_word(const uint32_t* P, const uint32_t* H, uint32_t x, int first) {
-  const uint32_t w = P[x];
-  if (first && w == x) {
-    const uint32_t h = H[x];
-    if (h != CL_NO_HOOK) return h;
-  }
-  return w;
-}
-
 // One compress pass of vertex v: an ancestor up to CL_WALK parents above the word of v.
 CL_HD uint32_t cl_walk(const uint32_t* P, const uint32_t* H, int n, uint32_t v, int first) {
-  uint32_t w = cl_word(P, H, v, first);
+  uint32_t w = bv_word(P, H, v, first);
   for (int t = 0; t < CL_WALK; ++t) {
     if (w == v || w >= (uint32_t)n) break;                           // v is a root
-    const uint32_t q = cl_word(P, H, w, first);
+    const uint32_t q = bv_word(P, H, w, first);
     if (q == w || q >= (uint32_t)n) break;                           // w is a root
     w = q;
   }

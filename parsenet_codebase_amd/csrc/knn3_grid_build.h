@@ -80,23 +80,6 @@ __device__ static inline KgGrid kg_segment_grid(const KgWs& w, int s, int n, int
   return kg_grid(n, lo, hi, ppc);
 }
 
-__device__ static inline uint32_t kg_wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ static inline uint32_t kg_wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 namespace {
 
 // ---- 1: bounding boxes and flags -----------------------------------------------------------------------------------
@@ -141,8 +124,8 @@ __global__ __launch_bounds__(256) void pn_knn3_grid_bbox_kernel(const float* __r
   if (!one) return;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    mn[a] = kg_wave_min_u32(mn[a]);
-    mx[a] = kg_wave_max_u32(mx[a]);
+    mn[a] = pn_wave_min_u32(mn[a]);
+    mx[a] = pn_wave_max_u32(mx[a]);
   }
   bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
   if (lane == 0) {

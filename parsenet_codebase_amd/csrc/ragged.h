@@ -1,7 +1,8 @@
 // What every kernel over a ragged batch needs besides its own arithmetic: the segment that a row or a tile belongs to,
-// and a workspace cut into typed arrays.  knn3_grid.hip, orient_global.hip and fps.hip take both from here.  Plain C++
-// behind RG_HD so that the same source is compiled into the gfx950 kernels and, by the test suite only
-// (tests/native/ragged_host.cpp), for the host.
+// and a workspace cut into typed arrays.  Every raw-cloud family takes them from here: knn3_grid.hip, knn3_query.hip
+// and register.hip through knn3_grid_build.h; fps.hip, outlier.hip, voxel.hip and plane.hip through fps_math.h;
+// cluster.hip, orient_global.hip and knn_lift.hip directly.  Plain C++ behind RG_HD so that the same source is compiled
+// into the gfx950 kernels and, by the test suite only (tests/native/ragged_host.cpp), for the host.
 //
 // A ragged batch is S segments over `total` rows: off[s] .. off[s + 1] - 1 are the rows of segment s, off ascends from
 // 0 to total, and a segment may be empty.  The offsets come from the caller, so a kernel never trusts them: it

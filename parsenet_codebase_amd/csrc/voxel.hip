@@ -104,23 +104,6 @@ __device__ static inline VxSeg vx_segment(const VxWs& w, int c, const float* __r
   return g;
 }
 
-__device__ static inline uint32_t vx_wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ static inline uint32_t vx_wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 __device__ static inline unsigned long long vx_peek(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -159,8 +142,8 @@ __global__ __launch_bounds__(VX_LANES) void pn_voxel_bounds_kernel(const float* 
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    mn[a] = vx_wave_min_u32(mn[a]);
-    mx[a] = vx_wave_max_u32(mx[a]);
+    mn[a] = pn_wave_min_u32(mn[a]);
+    mx[a] = pn_wave_max_u32(mx[a]);
   }
   bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
   if (pn_lane() == 0) {
